@@ -1,8 +1,16 @@
 #!/usr/bin/env python3
 """bench.py -- BASELINE.json's metric: CSR SpMV GFLOP/s + achieved HBM GB/s (% of roofline).
 
-  python bench.py [--gpus N --steps K --warmup W] [--workload spmv|spmm|spgemm|spmv_rmat]
+  python bench.py [--gpus N --steps K --warmup W] [--workload spmv|spmm|spgemm|spmv_rmat] [--full] [--dump-outputs DIR]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run sets up, warms up, times the K steps and prints the result line, nothing else.  --full adds everything
+else the benchmark measures and checks: the per-step event pass, a second (warm) inspect, the CPU baseline and the parity
+check of the timed y against the oracle, the `secondary` records (other BASELINE configs and operations), and for N > 1
+the `multi_gpu` breakdown and the parity check of the gathered y.  --dump-outputs DIR writes the y of the last timed step
+(what a caller of the timed path receives) to DIR/y.npy, or a fixed, seeded sample of it to DIR/y_sample.npy where the
+whole vector is larger than 60 MiB; the inputs are generated from fixed seeds, so two builds can be compared output for
+output.
 
 Default (N=1): cfg2 = fp32 CSR SpMV, 10M x 10M, exactly 10 nnz/row, columns iid uniform
 (unsorted), values/x U[0,1), int32 indices, inputs resident in HBM before the timed region.
@@ -56,9 +64,14 @@ def parse():
     p.add_argument("--debug-one-gpu", action="store_true",
                    help="debug/tests: all N ranks share cuda:0 with gloo as the process-group backend (RCCL refuses two "
                         "ranks on one device): exercises the N>1 code path end to end on a one-GPU box")
+    p.add_argument("--full", action="store_true",
+                   help="also run everything besides the headline: per-step events, warm inspect, CPU baseline + parity, "
+                        "secondary records, multi_gpu breakdown")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write the y of the last timed step as DIR/y.npy (or a seeded sample, DIR/y_sample.npy, above 60 MiB)")
     p.add_argument("--no-cpu-baseline", action="store_true")
     p.add_argument("--no-secondary", action="store_true",
-                   help="default N=1 cfg2 run only: skip the cfg4 / cfg3 / cfg5 / 8(f) records of the `secondary` object")
+                   help="--full N=1 cfg2 run only: skip the cfg4 / cfg3 / cfg5 / 8(f) records of the `secondary` object")
     p.add_argument("--full-line", action="store_true",
                    help="print the complete result object instead of the compact headline (tools/*.sh that read the plan)")
     p.add_argument("--no-8f", dest="no_8f", action="store_true",
@@ -171,10 +184,31 @@ def parity_spmv(y, y_ref, absrow, tol, row_len=None):
             "tol": tol, "worst_err_over_rownorm": ratio}
 
 
-def measure(step, steps, warmup, multi, device):
+DUMP_LIMIT_BYTES = 60 << 20  # 60 MiB: the files of one run stay under 64 MB
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: each device array as dirname/<name>.npy (float32 or float64, as computed).  An array larger than
+    DUMP_LIMIT_BYTES is written as <name>_sample.npy: the entries at a fixed, seeded, sorted set of indices, the same for
+    every run with the same arguments."""
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        h = a.detach().cpu().numpy()
+        assert h.dtype in (np.float32, np.float64), h.dtype
+        h = h.reshape(-1)
+        if h.nbytes > DUMP_LIMIT_BYTES:
+            keep = DUMP_LIMIT_BYTES // 2 // h.itemsize
+            idx = np.sort(np.random.default_rng(20240).choice(h.size, keep, replace=False))
+            h, name = h[idx], name + "_sample"
+        np.save(os.path.join(dirname, name + ".npy"), np.ascontiguousarray(h))
+
+
+def measure(step, steps, warmup, multi, device, keep=None):
     """W untimed steps, then EXACTLY K steps between barrier + synchronize on both sides; ONE pair of HIP events on
     the launch stream brackets the region (per-step event records were measured to cost up to 25 us per step).
-    Returns (wall seconds: max over ranks, average ms per step between the events)."""
+    Returns (wall seconds: max over ranks, average ms per step between the events).  keep: a list that receives a copy
+    of what the last timed step returned (taken after the region)."""
+    out = None
     for _ in range(warmup):
         step()
     torch.cuda.synchronize()
@@ -185,33 +219,35 @@ def measure(step, steps, warmup, multi, device):
     t0 = time.perf_counter()
     region[0].record()
     for _ in range(steps):
-        step()
+        out = step()
     region[1].record()
     torch.cuda.synchronize()
     if multi:
         dist.barrier()
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
+    if keep is not None:
+        keep.append(out.clone())
     el = torch.tensor([elapsed], dtype=torch.float64, device=device)
     if multi:
         dist.all_reduce(el, op=dist.ReduceOp.MAX)
     return float(el.item()), region[0].elapsed_time(region[1]) / steps
 
 
-def measure_guarded(op, step, steps, warmup, device):
+def measure_guarded(op, step, steps, warmup, device, keep=None):
     """measure() for a path that may fail on SOME ranks (the fused exchange on its first contact with N devices): every
     rank issues the same collectives whatever happens locally -- a short probe with a short time-out and an agreement, then
     the timed loop and a second agreement.  Returns (valid on every rank, wall seconds: max over ranks, ms per step between
     the events, the local exception or None).  Device-side waits are bounded (op._timeout), so a rank whose peers never
-    publish comes back with a time-out status instead of hanging."""
-    failed = None
+    publish comes back with a time-out status instead of hanging.  keep: as in measure()."""
+    failed, out = None, None
 
     def run(n):
-        nonlocal failed
+        nonlocal failed, out
         if failed is None:
             try:
                 for _ in range(n):
-                    step()
+                    out = step()
                 torch.cuda.synchronize()
                 op.check_status()
             except Exception as e:  # noqa: BLE001 - reported, the RCCL number stands
@@ -241,6 +277,8 @@ def measure_guarded(op, step, steps, warmup, device):
     torch.cuda.synchronize()
     el = torch.tensor([time.perf_counter() - t0], dtype=torch.float64, device=device)
     dist.all_reduce(el, op=dist.ReduceOp.MAX)
+    if keep is not None and failed is None and out is not None:
+        keep.append(out.clone())
     ok = agree()
     op._timeout = saved
     return ok, float(el.item()), region[0].elapsed_time(region[1]) / steps, failed
@@ -340,6 +378,8 @@ def main():
     args.handle_create_ms = (time.perf_counter() - t_h) * 1e3
 
     if args.workload in ("spmv_rmat1", "spmv_plain", "spmv_poisson1", "spmm", "spmm_banded", "spmm_rmat", "spgemm", "add", "transpose", "sptrsv", "csc_spmv", "spgemm4", "spmv_rmat_shards"):
+        if args.dump_outputs:
+            sys.exit(f"--dump-outputs: not available for --workload {args.workload} (spmv, spmv_poisson, spmv_rmat only)")
         from bench_extra import run_extra  # secondary configs (cfg3 / cfg5 / 8f rows), 1 GPU
         sys.stdout.flush()
         os.dup2(json_fd, 1)  # single-GPU secondary workloads print their own line
@@ -418,9 +458,12 @@ def main():
     # behind a collective-safe guard, checked again after its timed loop -- is valid AND faster.  A fused failure of any
     # kind (time-out, exception, mismatch) on any rank leaves the RCCL number as ms_per_step and exit code 0.
     fused_post_check, fused_elapsed, fused_kern_ms, fused_fail = None, None, None, None
+    # (--dump-outputs: a copy of the y of the last timed step of each timed path, taken after its region)
+    y_last, y_last_fused = ([], []) if args.dump_outputs else (None, None)
     if multi and mode == "fused" and rccl_op is not None:
-        rccl_elapsed, rccl_kern_ms = measure(lambda: rccl_op.step(x), args.steps, args.warmup, multi, device)
-        ok_f, fused_elapsed, fused_kern_ms, fused_fail = measure_guarded(op, lambda: op.step(x), args.steps, args.warmup, device)
+        rccl_elapsed, rccl_kern_ms = measure(lambda: rccl_op.step(x), args.steps, args.warmup, multi, device, keep=y_last)
+        ok_f, fused_elapsed, fused_kern_ms, fused_fail = measure_guarded(op, lambda: op.step(x), args.steps, args.warmup, device,
+                                                                         keep=y_last_fused)
         if ok_f:
             # ... and once more AFTER hundreds of steps, with vectors it has not seen, so that a peer store that only goes
             # stale under load cannot publish a number (every rank runs the same collectives whatever happens locally)
@@ -450,17 +493,23 @@ def main():
             elapsed, kern_avg_ms = rccl_elapsed, rccl_kern_ms
         elif fused_elapsed <= rccl_elapsed:
             elapsed, kern_avg_ms = fused_elapsed, fused_kern_ms
+            y_last = y_last_fused
         else:  # valid but slower than the library collective on this machine: the faster valid path is the timed one
             op, mode = rccl_op, "plain"
             elapsed, kern_avg_ms = rccl_elapsed, rccl_kern_ms
     else:
-        elapsed, kern_avg_ms = measure(lambda: op.step(x), args.steps, args.warmup, multi, device)
+        elapsed, kern_avg_ms = measure(lambda: op.step(x), args.steps, args.warmup, multi, device, keep=y_last)
         rccl_elapsed = elapsed if (multi and rccl_op is not None and op is rccl_op) else None
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"y": y_last[0]})
+    del y_last, y_last_fused
+
+    # Everything below up to the result line is --full only: a plain run reports the timed region alone.
 
     # Where the time of a multi-GPU step goes (outside the timed region, same K): the local kernels alone, the
     # all-gather alone, the RCCL step and -- when it could be set up -- the fused step.
     diag = None
-    if multi and rccl_op is not None:
+    if args.full and multi and rccl_op is not None:
         k = max(5, min(args.steps, 50))
         local_s, local_ev = measure(lambda: rccl_op.local(x), k, 2, multi, device)
         gather_s, _ = measure(lambda: rccl_op.gather(), k, 2, multi, device)
@@ -615,22 +664,24 @@ def main():
                 "note": "each figure: K steps between barriers, max over ranks; local = kernels only, gather = "
                         "collective only (y already computed), rccl_step = local + gather"}
     # Diagnostic pass outside the timed region: per-step events give the spread of single steps
-    ev = [[(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-           for _ in range(1 if mode in ("overlapped", "fused") or rmat else chunks)]
-          for _ in range(args.steps)]
-    for i in range(args.steps):
-        op.step(x, events=ev[i])
-    torch.cuda.synchronize()
-    if multi:
-        dist.barrier()
-    kern_ms = sorted(sum(a.elapsed_time(b) for a, b in step_ev) for step_ev in ev)
+    kern_ms = None
+    if args.full:
+        ev = [[(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
+               for _ in range(1 if mode in ("overlapped", "fused") or rmat else chunks)]
+              for _ in range(args.steps)]
+        for i in range(args.steps):
+            op.step(x, events=ev[i])
+        torch.cuda.synchronize()
+        if multi:
+            dist.barrier()
+        kern_ms = sorted(sum(a.elapsed_time(b) for a, b in step_ev) for step_ev in ev)
     values, rowptr, colind = a_chunks[0].values(), a_chunks[0].rowptr(), a_chunks[0].colind()
 
     # a second inspect of the same matrix (N = 1 only): the first one of a process also loads the code objects and
     # first-touches the pool, this one is what a caller pays from then on
     # (twice, the smaller figure: the first of the two still grows the memory pool by a second plan next to the live one)
     inspect_warm_ms = None
-    if not multi and args.alg != "noplan" and mode == "plain":
+    if args.full and not multi and args.alg != "noplan" and mode == "plain":
         y_tmp = torch.empty(rows_local, dtype=dtype, device=device)
         for _ in range(2):
             torch.cuda.synchronize()
@@ -643,14 +694,15 @@ def main():
         del y_tmp
 
     # What was timed is also what is checked (outside the timed region): y of the timed operator for this x.
-    y_timed = op.step(x)
-    torch.cuda.synchronize()
-    if fused_op is not None and mode == "fused":
-        fused_op.check_status()
-    y_timed = y_timed.clone()
-    parity = None
+    parity, y_timed = None, None
     tol = 1e-6 if tsize == 4 else 1e-12
-    if multi:
+    if args.full:
+        y_timed = op.step(x)
+        torch.cuda.synchronize()
+        if fused_op is not None and mode == "fused":
+            fused_op.check_status()
+        y_timed = y_timed.clone()
+    if args.full and multi:
         # N > 1: the gathered y of the timed path against PLAN-FREE local SpMVs (spmv_vector_kernel on the caller's own
         # arrays: no re-tiled copy, no plan) gathered by the plain RCCL path.  Both sides re-associate the row sums, so
         # the bound is 2 * tol * sum |a x| (the row norms come from the same plan-free kernel on |A|, |x|).
@@ -749,11 +801,12 @@ def main():
                          "kernel": kernels.get(alg_id, kernels[1]),
                          "algorithmic_bytes_per_launch": local_bytes, "kernel_avg_ms": kern_avg_ms,
                          "step_events_pass": {"note": "separate untimed pass with one event pair per step", "min_ms": kern_ms[0],
-                                              "median_ms": kern_ms[len(kern_ms) // 2], "avg_ms": sum(kern_ms) / len(kern_ms)},
+                                              "median_ms": kern_ms[len(kern_ms) // 2], "avg_ms": sum(kern_ms) / len(kern_ms)}
+                         if kern_ms else None,
                          "algorithmic_gbs_whole_step": spmv_bytes(m, n, nnz, tsize) / (elapsed / args.steps) / 1e9},
             "multi_gpu": diag,
         }
-        if world == 1 and chunks == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and chunks == 1 and not args.no_cpu_baseline:
             # the cpu_baseline leg computes the oracle's y for the same inputs; the timed plan's y is held to it
             y_ref, absrow, out["cpu_baseline"] = cpu_baseline_spmv(values, rowptr, colind, (m, n), x, nnz)
             if parity is None:
@@ -761,9 +814,9 @@ def main():
                 parity["against"] = "oracle_spmv (CPU restatement of multiply_impl.hpp:33-53), every row"
         else:
             out["cpu_baseline"] = None
-        out["parity_check"] = parity["status"] if parity else "not run (--no-cpu-baseline)"
+        out["parity_check"] = parity["status"] if parity else ("not run (--no-cpu-baseline)" if args.full else "not run (--full checks it)")
         out["parity"] = parity
-        if world == 1 and not multi and args.workload == "spmv" and args.rows is None and args.cols is None \
+        if args.full and world == 1 and not multi and args.workload == "spmv" and args.rows is None and args.cols is None \
                 and args.alg == "auto" and not args.no_secondary:
             # The other single-GPU BASELINE configs, after the timed cfg2 loop and its check, in the same process: cfg4
             # (1 GPU), cfg3, cfg5, then the SURVEY 8(f) operations add / transpose / triangular solve -- each inspected,
@@ -779,10 +832,11 @@ def main():
         # result -- every secondary record with its plan, roofline, cpu_baseline and parity report -- goes to
         # bench_secondary.json (next to this file, and under gpurun_out/ where that exists) and, one short line per
         # record, to stderr
+        # (--full only: a plain run writes no detail file, and its line names none, so the file always holds a --full record)
         from bench_line import compact, secondary_stderr_line
-        detail = "bench_secondary.json" if world == 1 else f"bench_secondary_n{world}.json"
+        detail = ("bench_secondary.json" if world == 1 else f"bench_secondary_n{world}.json") if args.full else None
         for d in (ROOT, os.path.join(ROOT, "gpurun_out")):
-            if os.path.isdir(d):
+            if detail and os.path.isdir(d):
                 try:
                     with open(os.path.join(d, detail), "w") as f:
                         json.dump(out, f, indent=1)

@@ -1,12 +1,14 @@
-"""Compile-check / run-check infrastructure for the drop-in backend headers (include/spblas/vendor/gfx950/*.hpp).
+"""Compile-check / run-check infrastructure for the drop-in backend headers (include/spblas/vendor/gfx950/*.hpp): the
+recipe for every binary that is compiled from the reference tree.  They all land in oracle/_ref/ (git-ignored), the one
+place whose build products travel to a machine without the reference tree; the sources they are built from (other than
+the reference's own) stay under tests/compile_check/.
 
 patched_reference_headers(dst)  applies INTEGRATION.md section 2's edits to a scratch copy of the six reference
                                 headers it names (nothing under /root/reference is written).
 build_dropin_run()              compiles tests/compile_check/dropin_run.cpp -- the reference's own <spblas/spblas.hpp>
                                 with -DSPBLAS_ENABLE_GFX950 -- and links it to libspblas_gfx950.so.  Only where the
-                                reference tree exists (the build container); the binary
-                                (tests/compile_check/_build/dropin_run, git-ignored) travels to the GPU box with the
-                                snapshot and tests/test_gpu_dropin.py runs it there.
+                                reference tree exists; the binary (oracle/_ref/dropin_run) is what
+                                tests/test_gpu_dropin.py runs on the GPU machine.
 The stubs under tests/compile_check/stubs/ stand in for range-v3's views::zip and for mdspan ONLY so that the
 reference's views and concepts parse; with a vendor backend selected none of the reference's algorithms is compiled in,
 and every expected value in dropin_run.cpp comes from host loops written in that file.  This is not a build of the
@@ -17,10 +19,10 @@ import shutil
 import subprocess
 import tempfile
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(os.path.dirname(HERE))
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+HERE = os.path.join(ROOT, "tests", "compile_check")  # the project's own sources of these builds
 REF = "/root/reference/include"
-OUT_DIR = os.path.join(HERE, "_build")
+OUT_DIR = os.path.join(ROOT, "oracle", "_ref")
 DROPIN_RUN = os.path.join(OUT_DIR, "dropin_run")
 REF_DEVICE_TESTS = os.path.join(OUT_DIR, "reference_device_tests")
 # the reference's own device tests, compiled UNMODIFIED from where they lie (never copied into this repository)
@@ -124,7 +126,7 @@ def build_dropin_run(libdir):
         scratch = patched_reference_headers(os.path.join(tmp, "patched"))
         cmd = [gxx, "-O1"] + compile_flags(scratch) + [
             os.path.join(HERE, "dropin_run.cpp"), "-L", libdir, "-lspblas_gfx950", "-L", os.path.join(rocm, "lib"),
-            "-lamdhip64", "-Wl,-rpath,$ORIGIN/../../../spblas-reference_amd/lib", "-Wl,-rpath," + os.path.join(rocm, "lib"),
+            "-lamdhip64", "-Wl,-rpath,$ORIGIN/../../spblas-reference_amd/lib", "-Wl,-rpath," + os.path.join(rocm, "lib"),
             "-o", DROPIN_RUN]
         r = subprocess.run(cmd, capture_output=True, text=True)
     if r.returncode != 0:
@@ -188,7 +190,7 @@ def build_reference_device_tests(libdir, jobs=4):
                 if r.returncode != 0:
                     raise RuntimeError(f"hipcc failed on {sources[i]}:\n" + r.stderr[-8000:])
         r = subprocess.run([hipcc, "--offload-arch=gfx950"] + objs + [
-            "-L", libdir, "-lspblas_gfx950", "-Wl,-rpath,$ORIGIN/../../../spblas-reference_amd/lib",
+            "-L", libdir, "-lspblas_gfx950", "-Wl,-rpath,$ORIGIN/../../spblas-reference_amd/lib",
             "-Wl,-rpath," + os.path.join(rocm, "lib"), "-o", REF_DEVICE_TESTS], capture_output=True, text=True)
     if r.returncode != 0:
         raise RuntimeError("link of reference_device_tests failed:\n" + r.stderr[-8000:])
@@ -222,7 +224,7 @@ def build_reference_examples(libdir):
             binp = os.path.join(OUT_DIR, name)
             r = subprocess.run([hipcc, "--offload-arch=gfx950", "-O1", "-Wno-reorder-ctor", "-DFMT_HEADER_ONLY", "-I", fmt] +
                                flags + [src, "-L", libdir, "-lspblas_gfx950",
-                                        "-Wl,-rpath,$ORIGIN/../../../spblas-reference_amd/lib",
+                                        "-Wl,-rpath,$ORIGIN/../../spblas-reference_amd/lib",
                                         "-Wl,-rpath," + os.path.join(rocm, "lib"), "-o", binp],
                                capture_output=True, text=True)
             if r.returncode != 0:
@@ -257,7 +259,7 @@ def build_reference_host_tests(libdir, jobs=4):
                 if r.returncode != 0:
                     raise RuntimeError(f"g++ failed on {sources[i]}:\n" + r.stderr[-8000:])
         r = subprocess.run([gxx] + objs + ["-L", libdir, "-lspblas_gfx950", "-L", os.path.join(rocm, "lib"), "-lamdhip64",
-                                           "-Wl,-rpath,$ORIGIN/../../../spblas-reference_amd/lib",
+                                           "-Wl,-rpath,$ORIGIN/../../spblas-reference_amd/lib",
                                            "-Wl,-rpath," + os.path.join(rocm, "lib"), "-o", REF_HOST_TESTS],
                            capture_output=True, text=True)
     if r.returncode != 0:
@@ -279,7 +281,7 @@ def build_reference_host_examples(libdir, jobs=4):
         scratch = patched_reference_headers(os.path.join(tmp, "patched"))
         common = [gxx, "-O1", "-DFMT_HEADER_ONLY", "-I", fmt] + compile_flags(scratch)
         tail = [os.path.join(HERE, "pinned_heap.cpp"), "-L", libdir, "-lspblas_gfx950", "-L", os.path.join(rocm, "lib"),
-                "-lamdhip64", "-Wl,-rpath,$ORIGIN/../../../spblas-reference_amd/lib", "-Wl,-rpath," + os.path.join(rocm, "lib")]
+                "-lamdhip64", "-Wl,-rpath,$ORIGIN/../../spblas-reference_amd/lib", "-Wl,-rpath," + os.path.join(rocm, "lib")]
 
         def build_one(name):
             binp = os.path.join(OUT_DIR, "ref_host_example_" + name)

@@ -3,9 +3,9 @@
 // Same translation environment as dropin_check.cpp -- the reference tree's <spblas/spblas.hpp> with
 // -DSPBLAS_ENABLE_GFX950 after INTEGRATION.md section 2's edits, include/spblas/vendor/gfx950/*.hpp as the vendor
 // backend -- but compiled to a program and linked to libspblas_gfx950.so.  It is built where the reference tree
-// exists (spblas-reference_amd/_build.py: build_dropin_run(), called from __graft_entry__.build()); the binary
-// (tests/compile_check/_build/dropin_run, git-ignored) travels to the GPU box with the snapshot and
-// tests/test_gpu_dropin.py runs it there.  Every operation is called exactly as a user of the reference would
+// exists (oracle/reference_build.py: build_dropin_run(), called from __graft_entry__.build()); the binary
+// (oracle/_ref/dropin_run, git-ignored) is what tests/test_gpu_dropin.py runs on the GPU machine, where the reference
+// tree does not exist.  Every operation is called exactly as a user of the reference would
 // (spblas::multiply(a, x, y), multiply_compute / multiply_fill, add, transpose, scale, triangular_solve on
 // spblas::csr_view over device pointers) and checked against plain host loops written here.
 #include <algorithm>

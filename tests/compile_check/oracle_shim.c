@@ -4,7 +4,7 @@
  *
  * TEST INFRASTRUCTURE ONLY.  Purpose: pin the oracle with the reference's OWN tests.  The reference's host test files
  * (test/gtest/{spmv,spmm,spgemm,spgemm_csr_csc,add,transpose,triangular_solve}_test.cpp) hold its known answers as
- * inline comparator loops; tests/compile_check/build_dropin.py compiles them unmodified against the drop-in header layer
+ * inline comparator loops; oracle/reference_build.py compiles them unmodified against the drop-in header layer
  * and links them to THIS library instead of libspblas_gfx950.so, so that spblas::multiply & co. end in oracle_spmv_*,
  * oracle_spmm_*, oracle_spgemm_*, oracle_add_*, oracle_transpose_*, oracle_trsv_*.  If those tests pass, the oracle
  * reproduces every known answer the reference's tests hold for this path (tests/test_oracle_reference_tests.py, CPU).

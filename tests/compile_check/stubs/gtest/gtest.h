@@ -1,4 +1,4 @@
-// TEST-RUN INFRASTRUCTURE ONLY (tests/compile_check/build_dropin.py: build_reference_device_tests()).
+// TEST-RUN INFRASTRUCTURE ONLY (oracle/reference_build.py: build_reference_device_tests()).
 // The image has no GoogleTest.  This is the handful of macros the reference's device tests use -- TEST,
 // EXPECT_EQ, EXPECT_NE, EXPECT_LE, EXPECT_NEAR -- with a registry and a main() (gtest_main.cpp), so that those test files can be compiled
 // UNMODIFIED from the reference tree against the gfx950 backend.  Not GoogleTest, pins nothing.

@@ -1,4 +1,4 @@
-// TEST INFRASTRUCTURE ONLY (tests/compile_check/build_dropin.py: build_reference_device_tests_on_oracle()).
+// TEST INFRASTRUCTURE ONLY (oracle/reference_build.py: build_reference_device_tests_on_oracle()).
 // The reference's DEVICE tests keep their operands in thrust::device_vector.  When those tests are linked to the CPU
 // oracle (oracle_shim.c) there is no device: this header stands in for <thrust/device_vector.h> with a host vector that
 // offers what the tests use -- construction from a std::vector / a size / another device_vector, data().get(),

@@ -68,3 +68,21 @@ def test_parity_report_bites():
     y_nan = y_ref.copy()
     y_nan[3] = np.nan  # a row the kernel never wrote
     assert bench.parity_spmv(y_nan, y_ref, absrow, 1e-6)["status"] == "fail"
+
+
+def test_dump_outputs_writes_whole_arrays_and_seeded_samples_of_large_ones(tmp_path, monkeypatch):
+    """--dump-outputs: an array under the limit is written whole, in its own float type; a larger one as a sample at fixed,
+    seeded indices, so two runs (two builds) with the same arguments write comparable files."""
+    import torch
+    bench = _bench()
+    small = torch.arange(1000, dtype=torch.float32)
+    big = torch.arange(5000, dtype=torch.float64)
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 8000)
+    bench.dump_outputs(str(tmp_path / "a"), {"y": small, "z": big})
+    bench.dump_outputs(str(tmp_path / "b"), {"z": big * 2})
+    y = np.load(tmp_path / "a" / "y.npy")
+    assert y.dtype == np.float32 and np.array_equal(y, small.numpy())
+    za, zb = np.load(tmp_path / "a" / "z_sample.npy"), np.load(tmp_path / "b" / "z_sample.npy")
+    assert za.dtype == np.float64 and za.nbytes <= 8000 and len(za) == 500
+    assert np.all(np.diff(za) > 0) and np.array_equal(zb, 2 * za)  # sorted entries at the same indices in both runs
+    assert not (tmp_path / "a" / "z.npy").exists()

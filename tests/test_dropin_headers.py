@@ -31,7 +31,7 @@ CHECK = os.path.join(ROOT, "tests", "compile_check")
 pytestmark = pytest.mark.skipif(not os.path.isdir(REF), reason="reference tree not present (GPU box)")
 
 
-from compile_check.build_dropin import compile_flags, patched_reference_headers  # noqa: E402
+from oracle.reference_build import compile_flags, patched_reference_headers  # noqa: E402
 
 
 def test_dropin_headers_compile_inside_the_reference_tree(tmp_path):
@@ -66,7 +66,7 @@ def test_cmake_module_configures_and_builds_the_backend():
     build of tests/compile_check/cmake_project, which links dropin_run.cpp through the INTERFACE target `spblas` the way the
     reference's CMakeLists.txt:80-88 links its rocSPARSE slot.  (The binary runs on the GPU in tests/test_gpu_dropin.py.)"""
     import spblas_reference_amd as sp
-    from compile_check.build_dropin import build_dropin_run_with_cmake
+    from oracle.reference_build import build_dropin_run_with_cmake
     if shutil.which("cmake") is None:
         pytest.skip("cmake not installed")
     if not os.path.exists(sp._build.LIBPATH):

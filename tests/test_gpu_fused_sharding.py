@@ -38,7 +38,10 @@ def test_fused_sharded_spmv_multiprocess(gpu, world, dt, stripes):
     assert r.returncode == 0 and "FUSED_OK" in r.stdout and "FUSED_VFREE_OK" in r.stdout, (r.stdout[-3000:], r.stderr[-3000:])
 
 
-@pytest.mark.parametrize("world,dt,chunks,tri", [(2, "f32", 4, 0), (4, "f32", 3, 0), (3, "f64", 2, 0), (8, "f32", 4, 0),
+# (at most four ranks, so that at most six processes hold the one GPU at a time: the ranks, the torch.distributed.run
+# launcher -- it asks for the device count, torch/distributed/launcher/api.py -- and the test process itself; an eight-rank
+# case held ten)
+@pytest.mark.parametrize("world,dt,chunks,tri", [(2, "f32", 4, 0), (4, "f32", 3, 0), (3, "f64", 2, 0), (4, "f32", 4, 0),
                                                  (4, "f32", 3, 1), (3, "f64", 2, 1)])
 def test_fused_dependent_chain_with_chunk_flags(gpu, world, dt, chunks, tri):
     """The dependent iteration y_{k+1} = A y_k without a step barrier: the reduce publishes a flag per (rank, chunk) after
@@ -49,7 +52,7 @@ def test_fused_dependent_chain_with_chunk_flags(gpu, world, dt, chunks, tri):
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", MASTER_ADDR="127.0.0.1", FUSED_STRIPES="1",
                FUSED_CHUNKS=str(chunks), FUSED_TRIANGULAR=str(tri))
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={world}",
-           "--master-addr", "127.0.0.1", "--master-port", str(29690 + world + (7 if dt == "f64" else 0) + 20 * tri),
+           "--master-addr", "127.0.0.1", "--master-port", str(29690 + world + (7 if dt == "f64" else 0) + 20 * tri + 100 * chunks),
            os.path.join(ROOT, "tests", "mp_fused_worker.py"), dt]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert r.returncode == 0 and "FUSED_OK" in r.stdout and f"chunks {chunks}" in r.stdout, (r.stdout[-3000:], r.stderr[-3000:])
@@ -77,7 +80,7 @@ def test_bench_multi_gpu_code_path_with_one_rank(gpu, fused):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=1", "--master-addr",
            "127.0.0.1", "--master-port", "29677" if fused == "auto" else "29678", os.path.join(ROOT, "bench.py"),
            "--gpus", "1", "--debug-multi", "--fused", fused, "--rows", "2000000", "--steps", "5", "--warmup", "2",
-           "--no-cpu-baseline"]
+           "--no-cpu-baseline", "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert r.returncode == 0 and len(lines) == 1, (r.stdout[-2000:], r.stderr[-2000:])
@@ -103,7 +106,7 @@ def test_bench_cfg4_rmat_multi_gpu_code_path_with_one_rank(gpu):
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", MASTER_ADDR="127.0.0.1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=1", "--master-addr",
            "127.0.0.1", "--master-port", "29679", os.path.join(ROOT, "bench.py"), "--gpus", "1", "--debug-multi",
-           "--workload", "spmv_rmat", "--rows", str(1 << 18), "--steps", "5", "--warmup", "2", "--no-cpu-baseline"]
+           "--workload", "spmv_rmat", "--rows", str(1 << 18), "--steps", "5", "--warmup", "2", "--no-cpu-baseline", "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert r.returncode == 0 and len(lines) == 1, (r.stdout[-2000:], r.stderr[-2000:])
@@ -120,7 +123,7 @@ def test_bench_launches_its_own_ranks_and_checks_what_it_timed(gpu, workload):
     import json
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--debug-multi", "--steps", "5", "--warmup", "2",
-           "--no-cpu-baseline", "--workload", workload, "--rows", "2000000" if workload == "spmv" else str(1 << 18)]
+           "--no-cpu-baseline", "--workload", workload, "--rows", "2000000" if workload == "spmv" else str(1 << 18), "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert r.returncode == 0 and len(lines) == 1, (r.stdout[-2000:], r.stderr[-2000:])
@@ -134,14 +137,49 @@ def test_bench_single_gpu_line_is_self_checking(gpu):
     """N = 1 (a reduced cfg2 so the test stays short): the y of the timed plan is compared with the oracle's y that the
     cpu_baseline leg computes anyway -- the published number and the checked number come from one process."""
     import json
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--rows", "1000000", "--steps", "5", "--warmup", "2"],
-                       capture_output=True, text=True, timeout=900, cwd=ROOT)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--rows", "1000000", "--steps", "5", "--warmup", "2",
+                        "--full"], capture_output=True, text=True, timeout=900, cwd=ROOT)
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert r.returncode == 0 and len(lines) == 1, (r.stdout[-2000:], r.stderr[-2000:])
     out = _bench_full(lines[0])
     assert out["parity_check"] == "pass" and out["parity"]["rows"] == 1000000
     assert out["cpu_baseline"]["cores"] == 1 and out["cpu_baseline"]["cpu_model"]
     assert out["multi_gpu"] is None
+
+
+def test_bench_plain_run_is_lean_and_dumps_the_timed_y(gpu, tmp_path):
+    """Without --full the run is the timed region alone: no CPU baseline, no parity check, no secondary records, no
+    per-step event pass, no detail file -- and --dump-outputs writes the y of the last timed step as it was computed (fp32,
+    every row), which must be A x for bench.py's own seeded inputs, held to the oracle row by row."""
+    import importlib.util
+    import json
+    import numpy as np
+    import torch
+    from oracle import oracle
+    m = 1000000
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--rows", str(m), "--steps", "3", "--warmup", "1",
+                        "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=900, cwd=ROOT)
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert r.returncode == 0 and len(lines) == 1, (r.stdout[-2000:], r.stderr[-2000:])
+    out = json.loads(lines[0])
+    assert out["steps"] == 3 and out["ms_per_step"] > 0 and out["value"] > 0 and out["dtype"] == "f32"
+    assert out["cpu_baseline"] is None and out["parity"] is None and "secondary_summary" not in out
+    assert "detail_file" not in out and out["config"]["inspect_warm_ms"] is None
+    y = np.load(tmp_path / "y.npy")
+    assert y.dtype == np.float32 and y.shape == (m,)
+    # the same inputs as bench.py's cfg2 at --rows m: its own row generator, x from the generator seeded 7
+    spec = importlib.util.spec_from_file_location("bench_inputs", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    v, rp, ci, nnz = bench.gen_rows(0, m, m, 10, False, torch.float32, gpu)
+    x = torch.rand(m, dtype=torch.float32, device=gpu, generator=torch.Generator(device=gpu).manual_seed(7))
+    vh, rph, cih, xh = v.cpu().numpy(), rp.cpu().numpy(), ci.cpu().numpy(), x.cpu().numpy()
+    assert nnz == 10 * m
+    y_ref = oracle.spmv((m, m), rph, cih, vh, xh)
+    absrow = oracle.spmv_absrow(rph, cih, vh, xh)
+    err = np.abs(y.astype(np.float64) - y_ref)
+    bad = ~(err <= 1e-6 * absrow + 1e-30)  # NaN fails
+    assert not bad.any(), (int(bad.sum()), float((err / np.maximum(absrow, 1e-300)).max()))
 
 
 @pytest.mark.parametrize("world,workload,fused", [(2, "spmv", "auto"), (4, "spmv", "auto"), (2, "spmv", "off"), (2, "spmv_rmat", "auto"), (3, "spmv_rmat", "auto")])
@@ -155,7 +193,7 @@ def test_bench_with_several_ranks_on_one_gpu(gpu, world, workload, fused):
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     rows = str(world * 600_000) if workload == "spmv" else str(1 << 18)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--debug-one-gpu", "--steps", "5", "--warmup",
-           "2", "--workload", workload, "--rows", rows, "--fused", fused]
+           "2", "--workload", workload, "--rows", rows, "--fused", fused, "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert r.returncode == 0 and len(lines) == 1 and r.stdout.strip() == lines[0], (r.stdout[-2000:], r.stderr[-3000:])
@@ -199,7 +237,7 @@ def test_bench_falls_back_to_rccl_when_a_rank_stops_publishing_its_flags(gpu, mu
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     env.update(SPBLAS_GFX950_TEST_MUTE_RANK="1", SPBLAS_GFX950_TEST_MUTE_AFTER=str(mute_after))
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--debug-one-gpu", "--steps", "5", "--warmup", "2",
-           "--rows", "1200000", "--fused", "auto", "--flag-chunks", "0"]
+           "--rows", "1200000", "--fused", "auto", "--flag-chunks", "0", "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert r.returncode == 0 and len(lines) == 1, (r.stdout[-2000:], r.stderr[-3000:])

@@ -20,8 +20,8 @@ import sys
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "tests"))
-from compile_check import build_dropin  # noqa: E402
+sys.path.insert(0, ROOT)
+from oracle import reference_build as build_dropin  # noqa: E402
 
 
 def test_oracle_passes_the_reference_host_tests():
@@ -109,7 +109,9 @@ def test_reference_tests_notice_an_oracle_that_stops_sorting(tmp_path):
     assert r.returncode == 0, r.stderr[-3000:]
     good = subprocess.run([binp], capture_output=True, text=True, timeout=900)
     assert good.returncode == 0 and "0 failed" in good.stdout
-    bad = subprocess.run([binp], capture_output=True, text=True, timeout=900, env=dict(os.environ, LD_PRELOAD=mutant))
+    # (the mutant goes first, in front of whatever the environment already preloads, which stays)
+    preload = ":".join(p for p in (mutant, os.environ.get("LD_PRELOAD", "")) if p)
+    bad = subprocess.run([binp], capture_output=True, text=True, timeout=900, env=dict(os.environ, LD_PRELOAD=preload))
     out = bad.stdout + bad.stderr
     assert bad.returncode != 0, "the reference's tests passed on an oracle that does not sort its rows"
     assert "not in ascending column order" in out, out[-3000:]

@@ -9,7 +9,7 @@ OUT=$ROOT/gpurun_out/ka_$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 for e in "${ENVS[@]}"; do export "$e"; done
-timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT -o ka -- python3 $ROOT/bench.py --steps 10 --warmup 2 --no-cpu-baseline "$@" > $OUT/run.log 2>&1
+timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT -o ka -- python3 $ROOT/bench.py --full --steps 10 --warmup 2 --no-cpu-baseline "$@" > $OUT/run.log 2>&1
 cd $ROOT
 tail -1 $OUT/run.log | cut -c1-1500
 python3 - <<PY

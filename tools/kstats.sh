@@ -10,7 +10,7 @@ OUT=$ROOT/gpurun_out/ks_$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 for e in "${ENVS[@]}"; do export "$e"; done
-timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT -o ks -- python3 $ROOT/bench.py --steps 20 --warmup 3 --no-cpu-baseline "$@" > $OUT/run.log 2>&1
+timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT -o ks -- python3 $ROOT/bench.py --full --steps 20 --warmup 3 --no-cpu-baseline "$@" > $OUT/run.log 2>&1
 cd $ROOT
 python3 - "$TAG" "${ENVS[*]}" <<PY
 import csv,glob,sys

@@ -2,7 +2,7 @@
 # HBM-side traffic of the kernels of one bench workload: tools/pmc_one.sh <tag> <bench args...>
 TAG=$1; shift
 ROOT=$(pwd); OUT=$ROOT/gpurun_out/pmc_$TAG; mkdir -p $OUT; cd /tmp; export TMPDIR=/tmp
-BENCH="python3 $ROOT/bench.py --steps 3 --warmup 1 --no-cpu-baseline $*"
+BENCH="python3 $ROOT/bench.py --full --steps 3 --warmup 1 --no-cpu-baseline $*"
 i=0
 for SET in "TCC_EA0_RDREQ_32B_sum TCC_EA0_RDREQ_64B_sum TCC_EA0_RDREQ_128B_sum TCC_EA0_WRREQ_sum" "TCC_EA0_WRREQ_64B_sum TCC_HIT_sum TCC_MISS_sum TCC_REQ_sum"; do
   i=$((i+1))

@@ -2,7 +2,7 @@
 # Issue-side counters (SQ / TA / TCP) of the kernels of one bench workload: tools/pmc_sq.sh <tag> <bench args...>
 TAG=$1; shift
 ROOT=$(pwd); OUT=$ROOT/gpurun_out/sq_$TAG; mkdir -p $OUT; cd /tmp; export TMPDIR=/tmp
-BENCH="python3 $ROOT/bench.py --steps 3 --warmup 1 --no-cpu-baseline $*"
+BENCH="python3 $ROOT/bench.py --full --steps 3 --warmup 1 --no-cpu-baseline $*"
 i=0
 for SET in \
   "SQ_WAVES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_VMEM_RD SQ_INSTS_LDS SQ_INSTS_BRANCH" \

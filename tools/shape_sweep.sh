@@ -26,7 +26,7 @@ run "RW=4 LDS=40 BINS=4096 (H~2.4k, 4 WG/CU)"   SPBLAS_GFX950_PB_RLDS_KB=40 SPBL
 run "default RBATCH=2"                          SPBLAS_GFX950_PB_RBATCH=2
 run "XLDS=80 (489 slices)"                      SPBLAS_GFX950_PB_XLDS_KB=80
 cd /tmp && export TMPDIR=/tmp
-timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/qs -o qs -- python3 $ROOT/bench.py --steps 10 --warmup 3 --no-cpu-baseline > $OUT/qs.log 2>&1
+timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/qs -o qs -- python3 $ROOT/bench.py --full --steps 10 --warmup 3 --no-cpu-baseline > $OUT/qs.log 2>&1
 cd $ROOT
 python3 - <<PY
 import csv,glob
