@@ -745,9 +745,10 @@ __global__ __launch_bounds__(NW * 64) void spmm_band_kernel(int64_t m, int64_t n
 // banded bench).  When a block fills its window densely enough (inspect: >= mm_band_dense_pm / 1000 of the 32 x W slots, W <=
 // the staged rows), a DENSE 32 x W tile of A in LDS (At[k][row], 16 KiB beside the 64 KiB B window: two workgroups per CU)
 // turns the same contraction into W / 4 steps of v_mfma_f32_16x16x4_f32 per wave and row half (wave w: output columns
-// 16 w .. 16 w + 15), whose operands are two 4-byte LDS reads per step.  Building At costs three LDS accesses per entry-lane
-// and no atomics: the rows of a wave are its own, every lane stores a TAG at its entry's slot, reads it back, and a slot
-// that holds another lane's tag is a duplicate (row, column) pair -- only then the wave falls back to LDS float adds.  A
+// 16 w .. 16 w + 15), whose operands are two 4-byte LDS reads per step.  Building At costs four LDS accesses per entry-lane
+// and no atomics: the rows of a wave are its own, every lane reads its entry's slot (non-zero: an earlier batch of 64 holds
+// the same column), stores a TAG there, reads it back, and a slot that holds another lane's tag is a duplicate (row,
+// column) pair -- only then the wave falls back to LDS float adds.  A
 // zero of At times a non-finite element of B would put a NaN into rows that do not reference that row of B (the reference
 // multiplies stored entries only, multiply_impl.hpp:85-91): a block whose result holds a non-finite value is computed
 // again entry by entry (plain loop, one row at a time), which has the reference's semantics.
@@ -812,6 +813,12 @@ __global__ __launch_bounds__(512) void spmm_band_mfma_kernel(int64_t m, int64_t 
         const int row = wave * RPW + i;
         lds_vint* slot = (lds_vint*) (reinterpret_cast<int*>(At) + row * CHs + ((cv - kb) ^ (2 * (row & 15))));
         const int tag = base + lane + 1;
+        // At was zeroed and tags start at 1: a slot that already holds a tag was claimed by an EARLIER batch of this row
+        // (a pair more than 64 entries apart), which the read-back below cannot see -- this batch overwrites it.  Lanes of
+        // one batch all read before any of them stores (one wave instruction, LDS operations of a wave in issue order),
+        // so a pair inside the batch reads 0 here and is caught by the read-back.
+        if (ok)
+          dup |= *slot != 0;
         if (ok)
           *slot = tag;
         if (ok)

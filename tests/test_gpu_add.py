@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 import torch
 
+import fullcheck as F
 import gpu_util as G
 import spblas_reference_amd as sp
 import util
@@ -422,3 +423,66 @@ def test_add_golden_bit_exact_by_rank(gpu, monkeypatch):
             cols.fill_(-1)
             sp.add_compute(info, A, B, d_c)
             assert np.array_equal(G.host(cols), g["c_colind"]) and np.array_equal(G.host(vals), g["c_values"])
+
+
+# ------------------------------------------------------------------------- SURVEY 8(f) sizes (bench.py --full workloads)
+def test_add_at_bench_size_every_row(gpu):
+    """C = A + B at the size bench.py --full times (1M x 1M, 16 entries per row each, seeds 0 / 1, columns unsorted and
+    values U[0,1) as generate.uniform_csr_device makes them): row offsets and columns EXACT against oracle.add over all
+    rows, every value within the parity bound."""
+    m = 1_000_000
+    av, ar, ac, ash, annz = generate.uniform_csr_device(m, m, 16, seed=0)
+    bv, br, bc, bsh, bnnz = generate.uniform_csr_device(m, m, 16, seed=1)
+    a, b = sp.csr_view(av, ar, ac, ash, annz), sp.csr_view(bv, br, bc, bsh, bnnz)
+    c_rp = torch.full((m + 1,), -1, dtype=torch.int32, device="cuda")
+    c = sp.csr_view(None, c_rp, None, (m, m), 0)
+    info = sp.add_inspect(a, b, c)
+    cn = info.result_nnz()
+    c.update(torch.full((cn,), float("nan"), device="cuda"), c_rp, torch.full((cn,), -1, dtype=torch.int32, device="cuda"),
+             (m, m), cn)
+    sp.add_compute(info, a, b, c)
+    a_h = (ar.cpu().numpy(), ac.cpu().numpy(), av.cpu().numpy())
+    b_h = (br.cpu().numpy(), bc.cpu().numpy(), bv.cpu().numpy())
+    r_rp, r_ci, r_v = oracle.add((m, m), *a_h, (m, m), *b_h)
+    _, _, r_abs = oracle.add((m, m), a_h[0], a_h[1], np.abs(a_h[2]), (m, m), b_h[0], b_h[1], np.abs(b_h[2]))
+    assert cn == int(r_rp[-1])
+    assert np.array_equal(G.host(c_rp), r_rp), "add at bench size: row offsets"
+    assert np.array_equal(G.host(c.colind()), r_ci[:cn]), "add at bench size: columns"
+    util.assert_parity(G.host(c.values()), r_v[:cn], r_abs[:cn].astype(np.float64), np.float32, row_len=np.full(cn, 2),
+                       what="add at bench size, every value")
+
+
+def test_spgemm_4args_at_bench_size_every_value(gpu, monkeypatch):
+    """C = alpha A B + beta D with alpha = 1.5, beta = -0.5 at cfg5's size (1M x 1M, 16 entries per row in A, B and D; D's
+    columns ascending within each row), the form bench.py --full times.  Every value of C against the float64 expansion
+    of all products and addend entries (tests/fullcheck.py), which pins C's structure too: once after multiply_compute,
+    once more through the fill without rank reuse that the benchmark times."""
+    m = 1_000_000
+    av, ar, ac, ash, annz = generate.uniform_csr_device(m, m, 16, seed=0)
+    bv, br, bc, bsh, bnnz = generate.uniform_csr_device(m, m, 16, seed=1)
+    dv, dr, dc, dsh, dnnz = generate.uniform_csr_device(m, m, 16, seed=2)
+    key = torch.repeat_interleave(torch.arange(m, device="cuda"), 16) * m + dc.long()
+    order = torch.argsort(key)
+    dc, dv = dc[order].contiguous(), dv[order].contiguous()
+    del key, order
+    a, b, d = sp.csr_view(av, ar, ac, ash, annz), sp.csr_view(bv, br, bc, bsh, bnnz), sp.csr_view(dv, dr, dc, dsh, dnnz)
+    alpha, beta = 1.5, -0.5
+    a_s, d_s = sp.scaled(alpha, a), sp.scaled(beta, d)
+    c_rp = torch.full((m + 1,), -1, dtype=torch.int32, device="cuda")
+    c = sp.csr_view(None, c_rp, None, (m, m), 0)
+    state = sp.spgemm_state_t()
+    sp.multiply_compute(state, a_s, b, c, d_s)
+    cn = state.result_nnz()
+    c.update(torch.full((cn,), float("nan"), device="cuda"), c_rp, torch.full((cn,), -1, dtype=torch.int32, device="cuda"),
+             (m, m), cn)
+    sp.multiply_fill(state, a_s, b, c, d_s)
+    c_ref, c_abs = F.spgemm_ref_f64((ar, ac, av), (br, bc, bv), c_rp, c.colind(), alpha=alpha, D=(dr, dc, dv), beta=beta)
+    F.assert_parity_t(c.values(), c_ref, c_abs, np.float32, what="4-argument SpGEMM at bench size, first fill")
+    first_cols = c.colind().clone()
+    monkeypatch.setenv("SPBLAS_GFX950_SPGEMM_REUSE", "0")
+    c.values().fill_(float("nan"))
+    sp.multiply_fill(state, a_s, b, c, d_s)
+    assert torch.equal(c.colind(), first_cols)
+    F.assert_parity_t(c.values(), c_ref, c_abs, np.float32, what="4-argument SpGEMM at bench size, fill without reuse")
+    del c_ref, c_abs, first_cols
+    torch.cuda.empty_cache()

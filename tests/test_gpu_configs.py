@@ -3,19 +3,23 @@
   cfg1  examples/simple_spmv.cpp plumbing case: fp32 CSR 10k x 10k, nnz = 1e6 (1 %), the reference generator's
         distribution (backend/generate.hpp:106-120) -- compared with the oracle in full, every algorithm
   cfg3  fp32 CSR x dense SpMM, A 2M x 2M 32 nnz/row, B 2M x 128 -- linearity + sampled rows vs the oracle,
-        plus an R-MAT A of the same size class (hub rows) against the same checks
+        plus an R-MAT A of the same size class (hub rows) against the same checks; every element of C against
+        the float64 reference of tests/fullcheck.py
   cfg4  fp64 CSR SpMV, R-MAT scale 24 (268 M entries) -- checksum, linearity, the 2 000 heaviest rows and
-        4 000 sampled rows vs the oracle at 1e-12 norm-wise, AUTO and forced SLICED
+        4 000 sampled rows vs the oracle at 1e-12 norm-wise, AUTO, row-block and forced SLICED; then every row,
+        and every row of a product with a signed x, against the host oracle
   cfg5  fp32 CSR x CSR SpGEMM 1M x 1M, 16 nnz/row -- nnz(C) and rowptr EXACT against a full oracle symbolic
-        run, sorted columns, (AB)x = A(Bx), sampled rows exact
+        run, sorted columns, (AB)x = A(Bx), sampled rows exact; every value of every fill against the float64
+        expansion of all products (tests/fullcheck.py), which pins every column index as well
 
-The oracle runs on the host only over what it finishes in seconds; everything at full
-size is checked through size-independent properties on the device.
+The host oracle runs over what it finishes in seconds; the rest of every full-size output is
+compared on the device with the float64 references of tests/fullcheck.py, which do not use the library's kernels.
 """
 import numpy as np
 import pytest
 import torch
 
+import fullcheck as F
 import gpu_util as G
 import spblas_reference_amd as sp
 import util
@@ -116,6 +120,13 @@ def test_cfg3_spmm_full_size(gpu, inspect):
     rows = np.unique(np.concatenate([np.arange(1500), np.arange(m - 1500, m),
                                      np.random.default_rng(0).integers(0, m, 1500)]))
     _check_spmm_rows(rows, rowptr, colind, values, B1, C1, f"cfg3 sampled rows (inspect={inspect})")
+    # every element of C against the float64 reference
+    del colsum, w, ref, B2
+    C_ref, C_abs = F.spmm_ref_f64(rowptr, colind, values, B1)
+    F.assert_parity_t(C1, C_ref, C_abs, np.float32, row_len=rowptr[1:].long() - rowptr[:-1].long(),
+                      what=f"cfg3 every element (inspect={inspect})")
+    del C_ref, C_abs
+    torch.cuda.empty_cache()
 
 
 def test_cfg3_spmm_rmat_hub_rows(gpu):
@@ -141,6 +152,11 @@ def test_cfg3_spmm_rmat_hub_rows(gpu):
     got = C[torch.from_numpy(rows.astype(np.int64)).cuda()].cpu().numpy()
     util.assert_parity(got, C_ref, 0.5 * _absprod_rows(sub_rp, inv.astype(np.int32), sub_v, B_sub), np.float32,
                        row_len=np.diff(sub_rp), what="cfg3 R-MAT heavy + sampled rows")
+    # every element of C against the float64 reference
+    C_full, C_abs = F.spmm_ref_f64(rowptr, colind, values, B, scale=0.5)
+    F.assert_parity_t(C, C_full, C_abs, np.float32, row_len=lens, what="cfg3 R-MAT every element")
+    del C_full, C_abs
+    torch.cuda.empty_cache()
     # the plan-free path gives the same answer to rounding
     C2 = torch.full((m, 128), float("nan"), device="cuda")
     sp.multiply(sp.scaled(0.5, a), B, C2)
@@ -200,6 +216,19 @@ def test_cfg4_spmv_rmat_scale24_f64(gpu, alg):
         y_ref = oracle.spmv((len(rows), n), sub_rp, sub_c, sub_v, x_h)
         absrow = oracle.spmv_absrow(sub_rp, sub_c, sub_v, x_h)
         util.assert_parity(y_h[rows], y_ref, absrow, np.float64, row_len=np.diff(sub_rp), what=f"cfg4 {alg} {what}")
+    # every row against the host oracle (single-threaded, fp64 sequential: a device float64 reference summed with atomics
+    # carries about k * eps * |row| of its own on the hub rows, the size of the bound), then a signed x on the same plan
+    del y2, y3, lin, tol
+    rp_h, ci_h, v_h = rowptr.cpu().numpy().astype(np.int32), colind.cpu().numpy(), values.cpu().numpy()
+    lens_h = np.diff(rp_h)
+    util.assert_parity(y_h, oracle.spmv(shape, rp_h, ci_h, v_h, x_h), oracle.spmv_absrow(rp_h, ci_h, v_h, x_h), np.float64,
+                       row_len=lens_h, what=f"cfg4 {alg} every row")
+    xs = x1 - 0.5
+    ys = torch.full((m,), float("nan"), dtype=torch.float64, device="cuda")
+    sp.multiply(info, a, xs, ys)
+    xs_h = xs.cpu().numpy()
+    util.assert_parity(G.host(ys), oracle.spmv(shape, rp_h, ci_h, v_h, xs_h), oracle.spmv_absrow(rp_h, ci_h, v_h, xs_h),
+                       np.float64, row_len=lens_h, what=f"cfg4 {alg} signed x, every row")
 
 
 def test_cfg4_matrix_transposed_without_a_plan_f64(gpu):
@@ -278,6 +307,12 @@ def test_cfg5_spgemm_full_size(gpu):
     got_rp, got_c, got_v = _rows_subproblem(rows, d_rp, d_c.colind(), d_c.values())
     assert np.array_equal(got_rp, cr) and np.array_equal(got_c, cc)
     np.testing.assert_allclose(got_v, cv, rtol=2e-5)
+    # every value of C against the float64 expansion of all 2.56e8 products, which also pins the structure: every product
+    # finds its (row, column) in C and every entry of C receives one
+    A_t, B_t = (ar, ac, av), (br, bc, bv)
+    c_ref, c_abs = F.spgemm_ref_f64(A_t, B_t, d_rp, d_c.colind())
+    F.assert_parity_t(d_c.values(), c_ref, c_abs, np.float32, what="cfg5 every value, first fill")
+    del c_ref, c_abs
     # numeric reuse (multiply_numeric after the first fill, vendor/rocsparse/multiply_spgemm.hpp:178-214): the second
     # pass accumulates by the product ranks recorded during the first one -- new values, fresh output arrays, same
     # structure; indices identical, values = 6 x the first result (A scaled by 2, B by 3: exact in binary)
@@ -285,6 +320,7 @@ def test_cfg5_spgemm_full_size(gpu):
     first_cols = d_c.colind().clone()
     av.mul_(2.0)
     bv.mul_(3.0)
+    c_ref, c_abs = F.spgemm_ref_f64(A_t, B_t, d_rp, first_cols)  # (3 * b rounds in fp32: recomputed, not 6x)
     d_c.update(torch.full((cn,), float("nan"), device="cuda"), d_rp,
                torch.full((cn,), -1, dtype=torch.int32, device="cuda"), (m, m), cn)
     for attempt in range(3):  # 2nd pass: hash + recording; 3rd and 4th: by rank (4th into the array the 3rd filled)
@@ -296,6 +332,9 @@ def test_cfg5_spgemm_full_size(gpu):
         sp.multiply_fill(info, d_a, d_b, d_c)
         assert torch.equal(d_c.colind(), first_cols), attempt
         assert bool(((d_c.values() - 6.0 * first_vals).abs() <= 1e-5 * (6.0 * first_vals).abs() + 1e-30).all()), attempt
+        F.assert_parity_t(d_c.values(), c_ref, c_abs, np.float32, what=f"cfg5 every value, reuse fill {attempt}")
+    del c_ref, c_abs
+    torch.cuda.empty_cache()
 
 
 def test_more_than_2_31_entries_need_64_bit_offsets(gpu):

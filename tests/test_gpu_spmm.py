@@ -210,6 +210,38 @@ def test_spmm_panel_path_matrix_cores(gpu, n, clusters, kernel, monkeypatch):
     assert bool(((C - C2).abs() <= 1e-5 * (C.abs() + C2.abs()) + 1e-6).all())
 
 
+@pytest.mark.parametrize("kernel", list(PANEL_KERNELS))
+def test_spmm_panel_path_repeated_pair_more_than_64_entries_apart(gpu, kernel, monkeypatch):
+    """A repeated (row, column) pair whose two entries sit in different batches of 64 (positions 3 and 90 of a 96-entry
+    row): both must be added, as the reference does (multiply_impl.hpp:85-91).  Rows of 96 distinct columns inside a +-48
+    window (no other repeat, so nothing else sends a wave to the duplicate path), the pair in every 7th row: some waves of
+    a block hold one, others none.  band_mfma's dense tile once kept only the later entry of such a pair."""
+    for k_, v_ in PANEL_KERNELS[kernel].items():
+        monkeypatch.setenv(k_, v_)
+    monkeypatch.setenv("SPBLAS_GFX950_SPMM_PANEL_MIN", "64")
+    rng = np.random.default_rng(23)
+    m = k = 8200
+    per_row, n = 96, 64
+    offs = np.argsort(rng.random((m, 97)), axis=1)[:, :per_row] - 48  # distinct offsets in [-48, 48] per row
+    cols = (np.arange(m)[:, None] + offs) % k
+    cols[::7, 90] = cols[::7, 3]
+    rowptr = (np.arange(m + 1) * per_row).astype(np.int32)
+    colind = cols.reshape(-1).astype(np.int32)
+    nnz = len(colind)
+    values = (rng.random(nnz) - 0.3).astype(np.float32)
+    B = (rng.random((k, n)) - 0.5).astype(np.float32)
+    a = G.csr_on_device(values, rowptr, colind, (m, k), nnz)
+    Bd = G.dev(B)
+    C = torch.full((m, n), float("nan"), device="cuda")
+    info = sp.multiply_inspect(sp.matrix_opt(a), Bd, C)
+    mi = info.state_.spmm_info()
+    assert mi["inspected"] == 1 and mi["panel_blocks"] >= 0.9 * (m // 32), mi
+    sp.multiply(info, sp.scaled(-1.5, a), Bd, C)
+    C_ref = oracle.spmm((m, k), rowptr, colind, values, B, scale_a=-1.5)
+    util.assert_parity(G.host(C), C_ref, 1.5 * absprod(values, rowptr, colind, (m, k), B), np.float32,
+                       row_len=np.diff(rowptr), what=f"panel spmm, pair 87 entries apart ({kernel})")
+
+
 def test_spmm_panel_threshold_default(gpu):
     """Default admission: >= 1/5 dense tiles go to the matrix cores, sparser banded blocks and uniform random
     columns stay with the row-group kernel (MFMA use 0 by construction for cfg3-like inputs)."""

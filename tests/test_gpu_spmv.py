@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 import torch
 
+import fullcheck as F
 import gpu_util as G
 import spblas_reference_amd as sp
 import util
@@ -613,7 +614,9 @@ def test_spmv_errors_on_device(gpu):
 def test_spmv_full_size_properties_cfg2(gpu, poisson):
     """BASELINE cfg2 (10M x 10M, avg 10 nnz/row, fp32) through size-independent properties:
     (1) a seeded sample of rows against the oracle, (2) linearity A(ax+by) = aAx + bAy,
-    (3) plan and plan-free kernels agree, (4) sum(y) == column-weighted checksum in fp64."""
+    (3) plan and plan-free kernels agree, (4) sum(y) == column-weighted checksum in fp64, and (5) every row of the sliced
+    and the row-block plan, and of the sliced plan once more on a signed x, against the float64 reference (tests/fullcheck.py):
+    a swapped pair of rows, a wrong slice boundary or a lost sign passes (1) - (4)."""
     m = n = 10_000_000
     values, rowptr, colind, shape, nnz = generate.uniform_csr_device(m, n, 10, poisson=poisson, seed=0)
     a = sp.csr_view(values, rowptr, colind, shape, nnz)
@@ -655,6 +658,19 @@ def test_spmv_full_size_properties_cfg2(gpu, poisson):
         y_ref = oracle.spmv((len(chunk), n), sub_rp, sub_c, sub_v, x_h)
         absrow = oracle.spmv_absrow(sub_rp, sub_c, sub_v, x_h)
         util.assert_parity(y_h[chunk], y_ref, absrow, np.float32, what="cfg2 sampled rows")
+    # (5) every row of both kernels against the float64 reference, then a signed x on the same plan, every row again
+    lens = rowptr[1:].long() - rowptr[:-1].long()
+    y_ref, absrow = F.spmv_ref_f64(rowptr, colind, values, x1)
+    F.assert_parity_t(y1, y_ref, absrow, np.float32, row_len=lens, what="cfg2 sliced plan, every row")
+    F.assert_parity_t(y1v, y_ref, absrow, np.float32, row_len=lens, what="cfg2 row-block plan, every row")
+    del y_ref, absrow, y2, y3
+    xs = x1 - 0.5
+    ys = torch.full((m,), float("nan"), device="cuda")
+    sp.multiply(info, a, xs, ys)
+    y_ref, absrow = F.spmv_ref_f64(rowptr, colind, values, xs)
+    F.assert_parity_t(ys, y_ref, absrow, np.float32, row_len=lens, what="cfg2 sliced plan, signed x, every row")
+    del y_ref, absrow
+    torch.cuda.empty_cache()
 
 
 @pytest.mark.parametrize("poisson", [False, True])
@@ -664,8 +680,9 @@ def test_spmv_full_size_plain_csr_view_reads_the_values_of_the_call_cfg2(gpu, po
     raw view that moves no version counter.  Every multiply must read the caller's array of that call
     (multiply_impl.hpp:48-52; vendor/rocsparse/detail/spmv_impl.hpp:72-77).  Checked by (1) 6 000 sampled rows (first / last
     2 000 + random) against the oracle, (2) the fp64 checksum of all of y against sum(values * x[colind]) on the device,
-    (3) agreement with the row-block kernel on the caller's arrays, all three after EACH rewrite, and (4) that the plan holds
-    no values (value_free, no update call made anywhere)."""
+    (3) agreement with the row-block kernel on the caller's arrays, (5) every row of both kernels against the float64
+    reference (tests/fullcheck.py), all four after EACH rewrite, and (4) that the plan holds no values (value_free, no update
+    call made anywhere)."""
     m = n = 10_000_000
     values, rowptr, colind, shape, nnz = generate.uniform_csr_device(m, n, 10, poisson=poisson, seed=0)
     a = sp.csr_view(values, rowptr, colind, shape, nnz)
@@ -686,6 +703,7 @@ def test_spmv_full_size_plain_csr_view_reads_the_values_of_the_call_cfg2(gpu, po
     x_h = x.cpu().numpy()
     rows_t = torch.from_numpy(rows).cuda()
     raw = torch.as_strided(values, values.shape, values.stride())
+    lens_d = rowptr[1:].long() - rowptr[:-1].long()
     for step, (mul, add) in enumerate(((1.0, 0.0), (-0.5, 0.125), (3.0, -1.0))):
         raw.data.mul_(mul).add_(add)                                # in place, after inspect; no update call anywhere
         y.fill_(float("nan"))
@@ -703,6 +721,11 @@ def test_spmv_full_size_plain_csr_view_reads_the_values_of_the_call_cfg2(gpu, po
             0, torch.repeat_interleave(torch.arange(m, device="cuda"), (rowptr[1:] - rowptr[:-1]).long()), prod.abs())
         assert bool(((y - yv).abs().double() <= 2e-6 * absy + 1e-30).all()), step
         del prod, absy
+        # every row of both kernels against the float64 reference of this call's values
+        y_ref, absrow = F.spmv_ref_f64(rowptr, colind, values, x)
+        F.assert_parity_t(y, y_ref, absrow, np.float32, row_len=lens_d, what=f"cfg2 plain csr_view, every row, rewrite {step}")
+        F.assert_parity_t(yv, y_ref, absrow, np.float32, row_len=lens_d, what=f"cfg2 row-block, every row, rewrite {step}")
+        del y_ref, absrow
 
 
 @pytest.mark.parametrize("offsets", [np.int32, np.int64])

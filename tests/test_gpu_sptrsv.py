@@ -327,3 +327,54 @@ def test_a_solve_that_gave_up_waiting_fails_the_next_solve_by_itself(gpu, monkey
     info.state_.check_status()
     ref = oracle.triangular_solve(M.shape, M.indptr, M.indices, vals, b, upper=False, unit=False)
     assert np.allclose(G.host(d_x), ref, rtol=1e-4, atol=1e-6)
+
+
+def test_lower_solve_at_bench_size_every_row(gpu):
+    """x = inv(L) b at the size bench.py --full times: 4M rows, 8 random entries per row at columns <= row (row 0's all
+    land on the diagonal), values U[-0.25, 0.25) / 8, and the diagonal 1 + U[0,1) stored LAST in every row -- the diagonal
+    the reference reads (last diagonal wins).  Every row: (1) the norm-wise backward error of check() above, evaluated in
+    float64 on the device over the triangle the reference reads; (2) the forward error against oracle.triangular_solve."""
+    m, k = 4_000_000, 8
+    g = torch.Generator(device="cuda").manual_seed(0)
+    rows = torch.arange(m, device="cuda").repeat_interleave(k)
+    cols = (torch.rand(m * k, device="cuda", generator=g, dtype=torch.float64) * rows.double()).long().clamp_(min=0)
+    cols = torch.minimum(cols, rows)
+    vals = (torch.rand(m * k, device="cuda", generator=g) - 0.5) * (0.5 / k)
+    rp = torch.arange(m + 1, device="cuda", dtype=torch.int64) * (k + 1)
+    colind = torch.empty(m * (k + 1), dtype=torch.int32, device="cuda")
+    values = torch.empty(m * (k + 1), device="cuda")
+    colind.view(m, k + 1)[:, :k] = cols.view(m, k).int()
+    colind.view(m, k + 1)[:, k] = torch.arange(m, device="cuda", dtype=torch.int32)
+    values.view(m, k + 1)[:, :k] = vals.view(m, k)
+    values.view(m, k + 1)[:, k] = 1.0 + torch.rand(m, device="cuda", generator=g)
+    del rows, cols, vals
+    nnz = m * (k + 1)
+    a = sp.csr_view(values, rp.int(), colind, (m, m), nnz)
+    b = torch.rand(m, device="cuda", generator=g)
+    x = torch.full((m,), float("nan"), device="cuda")
+    info = sp.triangular_solve_inspect(a, sp.lower_triangle, sp.explicit_diagonal, b, x)
+    sp.triangular_solve(info, a, sp.lower_triangle, sp.explicit_diagonal, b, x)
+    assert bool(torch.isfinite(x).all())
+    # (1) T = the strictly lower entries + the last diagonal entry of each row (earlier diagonal entries are not read)
+    row_of = torch.arange(m, device="cuda").repeat_interleave(k + 1)
+    pos = torch.arange(nnz, device="cuda") % (k + 1)
+    read = (colind.long() < row_of) | (pos == k)
+    xd, bd = x.double(), b.double()
+    term = torch.where(read, values.double() * xd[colind.long()], torch.zeros((), dtype=torch.float64, device="cuda"))
+    tx = torch.zeros(m, dtype=torch.float64, device="cuda").index_add_(0, row_of, term)
+    norm = bd.abs().index_add_(0, row_of, term.abs())
+    kk = torch.zeros(m, dtype=torch.float64, device="cuda").index_add_(0, row_of, read.double()) + 2
+    tol = torch.clamp(0.5 * kk * float(np.finfo(np.float32).eps), min=util.TOL[np.dtype(np.float32)])
+    resid = (tx - bd).abs()
+    bad = ~(resid <= tol * norm)
+    assert not bool(bad.any()), (f"{int(bad.sum())} rows out of the backward-error bound, first "
+                                 f"{torch.nonzero(bad).flatten()[:5].tolist()}")
+    del row_of, pos, read, term, tx, norm, kk, tol, resid, bad
+    # (2) every x_i against the oracle's sequential solve, the forward bound of check()
+    ref = oracle.triangular_solve((m, m), rp.int().cpu().numpy(), colind.cpu().numpy(), values.cpu().numpy(),
+                                  b.cpu().numpy()).astype(np.float64)
+    ftol = max(100 * util.TOL[np.dtype(np.float32)], 0.5 * (k + 3) * float(np.finfo(np.float32).eps))
+    scale = np.maximum(np.abs(ref), np.abs(ref).max() * 1e-3 + 1e-30)
+    err = np.abs(G.host(x).astype(np.float64) - ref) / scale
+    assert err.max() <= ftol, f"max rel err vs oracle {err.max()} at row {err.argmax()}"
+    torch.cuda.empty_cache()

@@ -128,6 +128,22 @@ def test_transpose_large_is_an_involution(gpu):
     assert bool(((y1 - y2).abs() <= 2e-6 * y1.abs() + 1e-30).all())
 
 
+def test_transpose_at_bench_size_is_bit_exact(gpu):
+    """B = A^T at the size bench.py --full times: 10M x 10M, 10 entries per row (generate.uniform_csr_device, seed 0).
+    Every row offset, column and value bit EXACT against oracle.transpose (the reference's stable counting sort)."""
+    m = 10_000_000
+    av, ar, ac, ash, annz = generate.uniform_csr_device(m, m, 10, seed=0)
+    a = sp.csr_view(av, ar, ac, ash, annz)
+    t_rp = torch.full((m + 1,), -1, dtype=torch.int32, device="cuda")
+    t_ci = torch.full((annz,), -1, dtype=torch.int32, device="cuda")
+    t_v = torch.full((annz,), float("nan"), device="cuda")
+    sp.transpose(a, sp.csr_view(t_v, t_rp, t_ci, (m, m), annz))
+    r_rp, r_ci, r_v = oracle.transpose((m, m), ar.cpu().numpy(), ac.cpu().numpy(), av.cpu().numpy())
+    assert np.array_equal(G.host(t_rp), r_rp), "transpose at bench size: row offsets"
+    assert np.array_equal(G.host(t_ci), r_ci), "transpose at bench size: columns"
+    assert np.array_equal(G.host(t_v).view(np.uint32), r_v.view(np.uint32)), "transpose at bench size: value bits"
+
+
 @pytest.mark.parametrize("alg", [_capi.SPMV_AUTO, _capi.SPMV_SLICED])
 def test_inspected_csc_operand_uses_regular_kernels(gpu, alg):
     # y = A x with A given as csc_view (test/gtest/spmv_test.cpp:110-208), inspect + execute
