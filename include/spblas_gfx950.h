@@ -70,7 +70,15 @@ typedef enum spblas_gfx950_status {
 
 typedef enum spblas_gfx950_datatype {
   SPBLAS_GFX950_F32 = 0, /* float  : vendor/rocsparse/types.hpp:42-44 */
-  SPBLAS_GFX950_F64 = 1  /* double : vendor/rocsparse/types.hpp:47-49 */
+  SPBLAS_GFX950_F64 = 1, /* double : vendor/rocsparse/types.hpp:47-49 */
+  /* complex, interleaved (re, im) like std::complex<float / double>; alpha / beta point at ONE complex host scalar.
+   * SpMV (op N) and SpMM on CSR with int32 columns only: spmv_plan_create (AUTO / VECTOR / ROWBLOCK; SLICED returns
+   * STATUS_NOT_SUPPORTED), spblas_gfx950_spmv[_conj], spblas_gfx950_spmm[_strided[_conj]].  The other entry points that take a
+   * value type (spgemm_numeric[_addend], csr_add_numeric, csr_transpose, scale, sptrsv_solve) return STATUS_NOT_SUPPORTED
+   * for them, before any other check; so do plan_update_values / plan_detach and the two-stage / multi-GPU calls on a
+   * complex plan. */
+  SPBLAS_GFX950_C32 = 2, /* std::complex<float>  */
+  SPBLAS_GFX950_C64 = 3  /* std::complex<double> */
 } spblas_gfx950_datatype;
 
 typedef enum spblas_gfx950_indextype {
@@ -247,6 +255,15 @@ int spblas_gfx950_spmv(spblas_gfx950_handle_t handle, spblas_gfx950_plan_t plan,
                        const int32_t* colind, const void* values, const void* x, const void* beta,
                        void* y, int offset_type, int value_type);
 
+/* Conjugated operands (complex types only): y = alpha * op'(A) * x' + beta * y with bit 0 of conj_flags = conj(A) (every stored
+ * value conjugated) and bit 1 = conj(x).  conj_flags = 0 is spblas_gfx950_spmv itself; non-zero flags with a real value type
+ * or bits above 1 return STATUS_INVALID_VALUE.  Complex values take op = N only (STATUS_NOT_SUPPORTED for op = T).  Products
+ * are the componentwise formula (ac - bd, ad + bc) with the conjugations folded in as sign flips, accumulated in the value
+ * type; no C Annex G inf / NaN recovery. */
+int spblas_gfx950_spmv_conj(spblas_gfx950_handle_t handle, spblas_gfx950_plan_t plan, int op, int64_t m, int64_t n,
+                            int64_t nnz, const void* alpha, const void* rowptr, const int32_t* colind, const void* values,
+                            const void* x, const void* beta, void* y, int offset_type, int value_type, int conj_flags);
+
 /* ---- multi-GPU: fused all-gather of y (second stage) -------------------- */
 /* One process per GPU; the reference has no multi-device path, so nothing is mirrored here.
  * ipc_alloc/export/open: every rank allocates its copy of the full y (and, with uncached = 1 because
@@ -344,6 +361,15 @@ int spblas_gfx950_spmm_strided(spblas_gfx950_handle_t handle, spblas_gfx950_plan
                                const int32_t* colind, const void* values, const void* B, int64_t b_row_stride,
                                int64_t b_col_stride, const void* beta, void* C, int64_t c_row_stride,
                                int64_t c_col_stride, int offset_type, int value_type);
+
+/* spblas_gfx950_spmm_strided with conjugated operands: bit 0 of conj_flags = conj(A), bit 1 = conj(B); the same rules as
+ * spblas_gfx950_spmv_conj.  Complex plans use the plan's long-row list (rows longer than its window are cut into parts);
+ * the matrix-core kernels are fp32 only. */
+int spblas_gfx950_spmm_strided_conj(spblas_gfx950_handle_t handle, spblas_gfx950_plan_t plan, int64_t m, int64_t k,
+                                    int64_t n, int64_t nnz, const void* alpha, const void* rowptr,
+                                    const int32_t* colind, const void* values, const void* B, int64_t b_row_stride,
+                                    int64_t b_col_stride, const void* beta, void* C, int64_t c_row_stride,
+                                    int64_t c_col_stride, int offset_type, int value_type, int conj_flags);
 
 /* ---- SpGEMM:  C = alpha * A * B   (CSR x CSR -> CSR, int32 indices) -------- */
 /* State object = spgemm_state_t (vendor/rocsparse/multiply_spgemm.hpp:28-230). */

@@ -24,7 +24,8 @@ HIP_ERROR = 7
 INSUFFICIENT_SPACE = 8
 PLAN_MISMATCH = 9
 
-F32, F64 = 0, 1
+F32, F64, C32, C64 = 0, 1, 2, 3
+CONJ_A, CONJ_X = 1, 2  # conj_flags bits of spblas_gfx950_spmv_conj / spblas_gfx950_spmm_strided_conj
 I32, I64 = 0, 1
 OP_N, OP_T = 0, 1
 LOWER, UPPER = 0, 1
@@ -65,6 +66,12 @@ PROTOTYPES = [
     ("spblas_gfx950_spmm_strided", c_int,
      [c_void_p, c_void_p, c_i64, c_i64, c_i64, c_i64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_i64,
       c_void_p, c_void_p, c_i64, c_i64, c_int, c_int]),
+    ("spblas_gfx950_spmv_conj", c_int,
+     [c_void_p, c_void_p, c_int, c_i64, c_i64, c_i64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+      c_void_p, c_int, c_int, c_int]),
+    ("spblas_gfx950_spmm_strided_conj", c_int,
+     [c_void_p, c_void_p, c_i64, c_i64, c_i64, c_i64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_i64,
+      c_void_p, c_void_p, c_i64, c_i64, c_int, c_int, c_int]),
     ("spblas_gfx950_spmm_inspect", c_int, [c_void_p, c_void_p]),
     ("spblas_gfx950_spmm_plan_info", c_int, [c_void_p, ctypes.POINTER(c_i64)]),
     ("spblas_gfx950_csr_transpose", c_int,

@@ -5,8 +5,9 @@ Same names, argument meaning and error behaviour as the reference (paths relativ
 
   csr_view / csc_view          views/csr_view.hpp:12-77, views/csc_view.hpp
   scaled / scaled_view         algorithms/scaled.hpp, views/scaled_view_impl.hpp:97-219
-  conjugated                   views/conjugated_view_impl.hpp (rejected by GPU backends,
-                               vendor/rocsparse/detail/spmv_impl.hpp:29-33)
+  conjugated                   views/conjugated_view_impl.hpp: taken for complex SpMV / SpMM operands (conj(A),
+                               conj(x / B) or both, in the kernels); a conjugated REAL operand is rejected with
+                               RuntimeError like the GPU slot does (vendor/rocsparse/detail/spmv_impl.hpp:29-33)
   transposed                   algorithms/transposed.hpp:7-21 (zero-copy CSR<->CSC relabel)
   matrix_opt                   views/matrix_opt_impl.hpp:14-93 (caches the inspect result)
   operation_info_t             detail/operation_info_t.hpp:28-104
@@ -22,6 +23,14 @@ exercised here and this Python layer is what the tests drive.  Device memory is
 held in torch CUDA tensors (plumbing only): a view wraps caller-owned tensors exactly
 as csr_view wraps caller-owned device pointers.  All compute goes through the C ABI
 (include/spblas_gfx950.h); nothing here computes on the CPU or through torch ops.
+
+Value types: float32 / float64 everywhere; complex64 / complex128 (std::complex<float / double>) for SpMV and SpMM on a
+csr_view with int32 column indices (int32 / int64 row offsets), plan-free or inspected (VECTOR / ROWBLOCK / AUTO plans,
+matrix_opt).  Complex operands may be conjugated -- conjugated(A), conjugated(x / B), or a tensor whose lazy conj bit is set
+(t.conj(): the bit is folded into the kernel's flag, nothing is copied) -- and scaled by complex factors: a factor counts
+conjugated iff an odd number of conjugated views wrap it (conjugated(scaled(s, A)) = conj(s) conj(A)).  Everything else with
+complex values -- csc_view / transposed() operands, int64 column indices, SpGEMM, add, transpose, scale, triangular_solve --
+raises TypeError; an output with the conj bit set raises ValueError.
 """
 import ctypes
 import threading
@@ -451,7 +460,25 @@ class spgemm_state_t:
 
 
 # --------------------------------------------------------------------------- helpers
-_VT = {torch.float32: (_capi.F32, ctypes.c_float), torch.float64: (_capi.F64, ctypes.c_double)}
+class _c_complex(ctypes.Structure):
+    """One complex host scalar (alpha / beta of a complex call): interleaved (re, im) like std::complex."""
+
+    def __init__(self, v=0):
+        v = complex(v)
+        super().__init__(v.real, v.imag)
+
+
+class c_complex64(_c_complex):
+    _fields_ = [("re", ctypes.c_float), ("im", ctypes.c_float)]
+
+
+class c_complex128(_c_complex):
+    _fields_ = [("re", ctypes.c_double), ("im", ctypes.c_double)]
+
+
+_VT = {torch.float32: (_capi.F32, ctypes.c_float), torch.float64: (_capi.F64, ctypes.c_double),
+       torch.complex64: (_capi.C32, c_complex64), torch.complex128: (_capi.C64, c_complex128)}
+_COMPLEX = (torch.complex64, torch.complex128)
 _OT = {torch.int32: _capi.I32, torch.int64: _capi.I64}
 
 
@@ -460,10 +487,128 @@ def _ptr(t):
         t.data_ptr() if t is not None else 0)
 
 
-def _vtype(t, what):
+def _vtype(t, what, complex_ok=False):
+    if t.dtype in _COMPLEX and not complex_ok:
+        raise TypeError(f"{what}: complex values are supported for SpMV / SpMM on csr_view operands only, got {t.dtype}")
     if t.dtype not in _VT:
-        raise TypeError(f"{what}: gfx950 backend supports float32/float64 values, got {t.dtype}")
+        raise TypeError(f"{what}: gfx950 backend supports float32/float64 values (complex64/complex128 for SpMV / SpMM), "
+                        f"got {t.dtype}")
     return _VT[t.dtype]
+
+
+def _is_complex_view(t):
+    base = get_ultimate_base(t)
+    vals = base if _is_tensor(base) else (base.values() if hasattr(base, "values") else None)
+    return vals is not None and vals.dtype in _COMPLEX
+
+
+def _reject_complex(what, *ts):
+    if any(_is_complex_view(t) for t in ts if t is not None):
+        raise TypeError(f"{what}: complex values are supported for SpMV / SpMM on csr_view operands only")
+
+
+def complex_scaling_factor(*ts):
+    """The scaling factor of complex operands: the product of every scaled() factor, each conjugated iff an odd number of
+    conjugated views wrap it (views/conjugated_view_impl.hpp: a conjugated view yields conj of whatever its base yields, so
+    conjugated(scaled(s, A)) is conj(s) * conj(A) while scaled(s, conjugated(A)) is s * conj(A)).  None without factors.
+    (get_scaling_factor, view_inspectors.hpp:22-77, multiplies the factors as they are: right for real operands only.)"""
+    out = None
+    for t in ts:
+        odd = False
+        while isinstance(t, (scaled_view, conjugated_view, matrix_opt)):
+            if isinstance(t, conjugated_view):
+                odd = not odd
+            elif isinstance(t, scaled_view):
+                f = complex(t.alpha())
+                f = f.conjugate() if odd else f
+                out = f if out is None else out * f
+            t = t.base()
+    return out
+
+
+def _complex_conj_flags(a, a_values, b, b_base, c):
+    """conj_flags of spblas_gfx950_spmv_conj / spmm_strided_conj for complex operands: conjugated views (parity rule of
+    is_conjugated) XOR the lazy conj bit of A's values and of x / B.  Returns (flags, x / B with its negative bit resolved)."""
+    if c.is_conj() or c.is_neg():
+        raise ValueError("multiply: the output must not be a lazily conjugated / negated tensor (resolve it first)")
+    if is_conjugated(c):
+        raise ValueError("multiply: the output cannot be a conjugated view")
+    ca = is_conjugated(a) ^ bool(a_values.is_conj())
+    cx = is_conjugated(b) ^ bool(b_base.is_conj())
+    # (torch's negative bit is resolved -- a copy, made only when the bit is set; the conj bit is kept and folded in)
+    return (_capi.CONJ_A if ca else 0) | (_capi.CONJ_X if cx else 0), a_values.resolve_neg(), b_base.resolve_neg()
+
+
+def _complex_operand(a, what):
+    a_base = get_ultimate_base(a)
+    if not isinstance(a_base, csr_view):
+        raise TypeError(f"{what}: complex values take a csr_view operand (csc_view / transposed(): not supported)")
+    if a_base.colind() is not None and a_base.colind().dtype != torch.int32:
+        raise TypeError(f"{what}: complex values take int32 column indices only")
+    _check_csr(a_base, what)
+    return a_base
+
+
+def _spmv_complex(info, a, b, c, prepare_only):
+    """_spmv for complex64 / complex128 operands (spblas_gfx950_spmv_conj)."""
+    a_base, b_base = _complex_operand(a, "multiply"), get_ultimate_base(b)
+    if not _is_tensor(c) or c.dim() != 1:
+        raise TypeError("multiply: the output vector must be a plain 1-D device tensor")
+    if a_base.shape()[0] != c.shape[0] or a_base.shape()[1] != b_base.shape[0]:
+        raise ValueError("multiply: matrix and vector dimensions are incompatible.")
+    vt, ct = _vtype(a_base.values(), "multiply", complex_ok=True)
+    if b_base.dtype != a_base.values().dtype or c.dtype != a_base.values().dtype:
+        raise TypeError("multiply: A, x and y must share one value type")
+    if not (b_base.is_contiguous() and c.is_contiguous()):
+        raise ValueError("multiply: x and y must be contiguous")
+    flags, a_vals, x = _complex_conj_flags(a, a_base.values(), b, b_base, c)
+    alpha_opt = complex_scaling_factor(a, b)
+    alpha, beta = ct(1 if alpha_opt is None else alpha_opt), ct(0)
+    hd = _Handle.current(c.device)
+    plan = _find_plan(info, a, a_base)
+    m, n = a_base.shape()
+    args = (hd.h, plan.plan if plan else None, _capi.OP_N, m, n, a_base.size(), ctypes.byref(alpha), _ptr(a_base.rowptr()),
+            _ptr(a_base.colind()), _ptr(a_vals), _ptr(x), ctypes.byref(beta), _ptr(c), _OT[a_base.rowptr().dtype], vt, flags)
+    if prepare_only:  # (the entry point with its bound arguments, and what keeps the operands alive)
+        return (_capi.lib().spblas_gfx950_spmv_conj, args), (alpha, beta, plan, a, b, c, a_vals, x)
+    check(_capi.lib().spblas_gfx950_spmv_conj(*args), "multiply")
+
+
+def _spmm_complex(info, a, b, c):
+    """_spmm for complex64 / complex128 operands (spblas_gfx950_spmm_strided_conj)."""
+    a_base, b_base = _complex_operand(a, "multiply"), get_ultimate_base(b)
+    if not _is_tensor(c) or c.dim() != 2:
+        raise TypeError("multiply: the output matrix must be a plain 2-D device tensor")
+    if (a_base.shape()[0] != c.shape[0] or b_base.shape[1] != c.shape[1]
+            or a_base.shape()[1] != b_base.shape[0]):
+        raise ValueError("multiply: matrix dimensions are incompatible.")
+    vt, ct = _vtype(a_base.values(), "multiply", complex_ok=True)
+    if b_base.dtype != a_base.values().dtype or c.dtype != a_base.values().dtype:
+        raise TypeError("multiply: A, B and C must share one value type")
+    flags, a_vals, bb = _complex_conj_flags(a, a_base.values(), b, b_base, c)
+    m, k = a_base.shape()
+    n = c.shape[1]
+    (brs, bcs), (crs, ccs) = _dense_strides(bb, k, n), _dense_strides(c, m, n)
+    alpha_opt = complex_scaling_factor(a, b)
+    alpha, beta = ct(1 if alpha_opt is None else alpha_opt), ct(0)
+    plan = _find_plan(info, a, a_base)
+    hd = _Handle.current(c.device)
+    check(_capi.lib().spblas_gfx950_spmm_strided_conj(hd.h, plan.plan if plan is not None else None, m, k, n, a_base.size(),
+                                                      ctypes.byref(alpha), _ptr(a_base.rowptr()), _ptr(a_base.colind()),
+                                                      _ptr(a_vals), _ptr(bb), brs, bcs, ctypes.byref(beta), _ptr(c), crs, ccs,
+                                                      _OT[a_base.rowptr().dtype], vt, flags), "multiply")
+
+
+def _dense_strides(t, rows, n):
+    """(row stride, column stride) of a layout_right or layout_left dense operand with `rows` rows and n columns."""
+    if t.numel() == 0:
+        return max(n, 1), 1
+    rs, cs = t.stride(0), t.stride(1)
+    if (cs == 1 or n <= 1) and (rows <= 1 or rs >= n):      # layout_right, possibly a column window (rs > n)
+        return (rs if rows > 1 else max(n, 1)), 1
+    if (rs == 1 or rows <= 1) and (n <= 1 or cs >= rows):   # layout_left, possibly a row window (cs > rows)
+        return 1, (cs if n > 1 else max(rows, 1))
+    raise ValueError("multiply: dense operands must be row-major (layout_right) or column-major (layout_left)")
 
 
 _NARROWED = {}  # id of an int64 index tensor -> (the tensor, its int32 copy); a handful of entries, oldest dropped first
@@ -479,6 +624,8 @@ def _int32_columns(a, what):
     idx = a.colind() if csr else a.rowind()
     if idx is None or idx.dtype != torch.int64:
         return a
+    if a.values() is not None and a.values().dtype in _COMPLEX:
+        raise TypeError(f"{what}: complex values take int32 column indices only")
     hit = _NARROWED.get(id(idx))
     if hit is None or hit[0] is not idx:
         bound = a.shape()[1] if csr else a.shape()[0]
@@ -522,7 +669,7 @@ def _build_plan(a_base, alg=_capi.SPMV_AUTO, snapshot=0):
     """snapshot: the value of SPBLAS_GFX950_OPT_VALUE_SNAPSHOT -- 1 / True: AUTO may choose the plan that keeps a re-tiled
     copy of the values (matrix_opt operands); 2: and the plan keeps its source positions from the start."""
     hd = _Handle.current(a_base.rowptr().device)
-    vt, _ = _vtype(a_base.values(), "multiply_inspect")
+    vt, _ = _vtype(a_base.values(), "multiply_inspect", complex_ok=True)
     plan = ctypes.c_void_p()
     m, n = a_base.shape()
     hd.set_option(_capi.OPT_VALUE_SNAPSHOT, int(snapshot))
@@ -675,6 +822,8 @@ def _find_plan(info, a, a_base):
 
 # --------------------------------------------------------------------------- SpMV / SpMM
 def _spmv(info, a, b, c, prepare_only=False):
+    if _is_complex_view(a) or _is_complex_view(b):
+        return _spmv_complex(info, a, b, c, prepare_only)
     a_base, b_base = get_ultimate_base(a), get_ultimate_base(b)
     a_base = _int32_columns(a_base, "multiply")
     _reject_conjugated(a, b, c)
@@ -721,8 +870,8 @@ def _spmv(info, a, b, c, prepare_only=False):
         args = (hd.h, plan.plan if plan else None, op, m, n, a_csr.size(), ctypes.byref(alpha), _ptr(a_csr.rowptr()),
                 _ptr(a_csr.colind()), _ptr(a_csr.values()), _ptr(b_base), ctypes.byref(beta), _ptr(c),
                 _OT[a_csr.rowptr().dtype], vt)
-    if prepare_only:
-        return args, (alpha, beta, plan, a, b, c)  # keep the operands alive with the bound call
+    if prepare_only:  # the entry point with its bound arguments; keep the operands alive with the bound call
+        return (_capi.lib().spblas_gfx950_spmv, args), (alpha, beta, plan, a, b, c)
     check(_capi.lib().spblas_gfx950_spmv(*args), "multiply")
 
 
@@ -735,8 +884,7 @@ class prepared_multiply:
     workspaces and must not run on two streams at once."""
 
     def __init__(self, info, a, x, y):
-        self._args, self._keep = _spmv(info, a, x, y, prepare_only=True)
-        self._fn = _capi.lib().spblas_gfx950_spmv
+        (self._fn, self._args), self._keep = _spmv(info, a, x, y, prepare_only=True)
         self._set_stream = _capi.lib().spblas_gfx950_set_stream
         self._stream = ctypes.c_void_p(torch.cuda.current_stream(y.device).cuda_stream)
         a_base = get_ultimate_base(a)
@@ -753,6 +901,8 @@ class prepared_multiply:
 
 
 def _spmm(info, a, b, c):
+    if _is_complex_view(a) or _is_complex_view(b):
+        return _spmm_complex(info, a, b, c)
     a_base, b_base = get_ultimate_base(a), get_ultimate_base(b)
     a_base = _int32_columns(a_base, "multiply")
     _reject_conjugated(a, b, c)
@@ -786,17 +936,7 @@ def _spmm(info, a, b, c):
     m, k = a_base.shape()
     n = c.shape[1]
 
-    def strides(t, rows):
-        if t.numel() == 0:
-            return max(n, 1), 1
-        rs, cs = t.stride(0), t.stride(1)
-        if (cs == 1 or n <= 1) and (rows <= 1 or rs >= n):      # layout_right, possibly a column window (rs > n)
-            return (rs if rows > 1 else max(n, 1)), 1
-        if (rs == 1 or rows <= 1) and (n <= 1 or cs >= rows):   # layout_left, possibly a row window (cs > rows)
-            return 1, (cs if n > 1 else max(rows, 1))
-        raise ValueError("multiply: dense operands must be row-major (layout_right) or column-major (layout_left)")
-
-    (brs, bcs), (crs, ccs) = strides(b_base, k), strides(c, m)
+    (brs, bcs), (crs, ccs) = _dense_strides(b_base, k, n), _dense_strides(c, m, n)
     alpha_opt = get_scaling_factor(a, b)
     alpha, beta = ct(1 if alpha_opt is None else alpha_opt), ct(0)
     hd = _Handle.current(c.device)
@@ -856,7 +996,10 @@ def multiply_inspect(*args, alg=_capi.SPMV_AUTO, values_will_change=False):
     if isinstance(info, spgemm_state_t):
         return None  # vendor/rocsparse/multiply_spgemm.hpp:232-235: no-op
     a_base = get_ultimate_base(a)
-    _reject_conjugated(a, b, c)
+    if _is_complex_view(a) and not _is_sparse(b):  # conjugated complex operands are taken (csr_view only)
+        a_base = _complex_operand(a, "multiply_inspect")
+    else:
+        _reject_conjugated(a, b, c)
     if isinstance(a_base, (csr_view, csc_view)) and not _is_sparse(b) and a_base.values() is not None:
         a_base = _int32_columns(a_base, "multiply_inspect")
     if isinstance(a_base, csr_view) and not _is_sparse(b) and a_base.values() is not None:
@@ -912,6 +1055,7 @@ def _spgemm_operands(a, b, c, d=None):
     arrays.  Operands stored the other way round are transposed on the device for this call.
     Returns (a_eff, b_eff, c_eff, d_eff)."""
     a_base, b_base = get_ultimate_base(a), get_ultimate_base(b)
+    _reject_complex("multiply_compute", a, b, c, d)
     if not isinstance(c, (csr_view, csc_view)):
         raise NotImplementedError("gfx950 SpGEMM result must be a csr_view or csc_view")
     _reject_conjugated(a, b)
@@ -1066,6 +1210,7 @@ def multiply_numeric(state, a, b, c, d=None):
 # --------------------------------------------------------------------------- add
 def _add_operands(a, b, c):
     a_base, b_base = get_ultimate_base(a), get_ultimate_base(b)
+    _reject_complex("add", a, b, c)
     if not (isinstance(a_base, csr_view) and isinstance(b_base, csr_view) and isinstance(c, csr_view)):
         raise NotImplementedError("gfx950 add supports CSR + CSR -> CSR")
     _reject_conjugated(a, b)
@@ -1196,6 +1341,7 @@ class _TrsvPlan:
 
 def _trsv_operands(a, uplo, diag, b, x):
     a_base = get_ultimate_base(a)
+    _reject_complex("triangular_solve", a, b, x)
     if not isinstance(a_base, csr_view):
         raise NotImplementedError("gfx950 triangular_solve supports csr_view operands")
     _reject_conjugated(a, b, x)

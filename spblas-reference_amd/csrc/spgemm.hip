@@ -28,6 +28,7 @@
 // (kk, 1), the product is the A entry itself) and D := the second summand.  add_inspect is the
 // symbolic pass, add_compute the numeric one; columns come out ascending like the CPU SPA + sort.
 #include "common.hpp"
+#include "complex_api.hpp"
 #include <type_traits>
 #include "scan.hpp"
 
@@ -2137,6 +2138,8 @@ int spblas_gfx950_spgemm_numeric(spblas_gfx950_handle_t handle, spblas_gfx950_sp
                                  const int32_t* b_rowptr, const int32_t* b_colind, const void* b_values,
                                  int32_t* c_rowptr, int32_t* c_colind, void* c_values, int64_t c_capacity,
                                  int value_type) {
+  if (is_complex_type(value_type))  // complex values: SpMV / SpMM only (complex.hip)
+    return SPBLAS_GFX950_STATUS_NOT_SUPPORTED;
   return spgemm_numeric_impl(handle, st, alpha, a_rowptr, a_colind, a_values, b_rowptr, b_colind, b_values, nullptr,
                              nullptr, nullptr, nullptr, c_rowptr, c_colind, c_values, c_capacity, value_type);
 }
@@ -2147,6 +2150,8 @@ int spblas_gfx950_spgemm_numeric_addend(spblas_gfx950_handle_t handle, spblas_gf
                                         const void* beta, const int32_t* d_rowptr, const int32_t* d_colind,
                                         const void* d_values, int32_t* c_rowptr, int32_t* c_colind, void* c_values,
                                         int64_t c_capacity, int value_type) {
+  if (is_complex_type(value_type))  // complex values: SpMV / SpMM only (complex.hip)
+    return SPBLAS_GFX950_STATUS_NOT_SUPPORTED;
   if (!d_rowptr)
     return SPBLAS_GFX950_STATUS_INVALID_POINTER;
   return spgemm_numeric_impl(handle, st, alpha, a_rowptr, a_colind, a_values, b_rowptr, b_colind, b_values, beta,
@@ -2174,6 +2179,8 @@ int spblas_gfx950_csr_add_numeric(spblas_gfx950_handle_t handle, spblas_gfx950_s
                                   const void* beta, const int32_t* b_rowptr, const int32_t* b_colind,
                                   const void* b_values, int32_t* c_rowptr, int32_t* c_colind, void* c_values,
                                   int64_t c_capacity, int value_type) {
+  if (is_complex_type(value_type))  // complex values: SpMV / SpMM only (complex.hip)
+    return SPBLAS_GFX950_STATUS_NOT_SUPPORTED;
   if (!b_rowptr)
     return SPBLAS_GFX950_STATUS_INVALID_POINTER;
   return spgemm_numeric_impl(handle, st, alpha, a_rowptr, a_colind, a_values, nullptr, nullptr, nullptr, beta,

@@ -24,6 +24,7 @@
 //                          by construction.
 // Algorithmic bytes = nnz*(sizeof(T)+4) + (m+1)*sizeof(O) + (k*n + m*n)*sizeof(T).
 #include "common.hpp"
+#include "complex_api.hpp"
 #include "plan.hpp"
 #include "scan.hpp"
 
@@ -1277,6 +1278,9 @@ extern "C" int spblas_gfx950_spmm(spblas_gfx950_handle_t handle, spblas_gfx950_p
                                   int64_t n, int64_t nnz, const void* alpha, const void* rowptr,
                                   const int32_t* colind, const void* values, const void* B, int64_t ldb,
                                   const void* beta, void* C, int64_t ldc, int offset_type, int value_type) {
+  if (is_complex_type(value_type))  // complex.hip, nothing conjugated (layout_right with leading dimensions ldb / ldc)
+    return spblas_gfx950_spmm_strided_conj(handle, plan, m, k, n, nnz, alpha, rowptr, colind, values, B, ldb, 1, beta, C, ldc, 1,
+                                           offset_type, value_type, 0);
   if (!handle)
     return SPBLAS_GFX950_STATUS_INVALID_HANDLE;
   if (m < 0 || k < 0 || n < 0 || nnz < 0 || m > INT32_MAX || k > INT32_MAX || ldb < n || ldc < n)
@@ -1310,6 +1314,9 @@ extern "C" int spblas_gfx950_spmm_strided(spblas_gfx950_handle_t handle, spblas_
                                           const int32_t* colind, const void* values, const void* B, int64_t brs, int64_t bcs,
                                           const void* beta, void* C, int64_t crs, int64_t ccs, int offset_type,
                                           int value_type) {
+  if (is_complex_type(value_type))
+    return spblas_gfx950_spmm_strided_conj(handle, plan, m, k, n, nnz, alpha, rowptr, colind, values, B, brs, bcs, beta, C, crs,
+                                           ccs, offset_type, value_type, 0);
   if (bcs == 1 && ccs == 1) {  // both layout_right: the regular kernels, plan included
     // (a layout_left mdspan with ONE row also has strides (1, 1): its row stride says nothing -- an operand of at most one
     // row gets the leading dimension the regular entry point asks for; round-4 advisor finding)

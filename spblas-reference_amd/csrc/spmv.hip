@@ -15,6 +15,7 @@
 //   spmv_long_fixup_kernel sums the per-window partials of rows longer than a window.
 //   spmv_transpose_kernel  op = T (CSC / transposed(csr)): scatter with HW float atomics.
 #include "common.hpp"
+#include "complex_api.hpp"
 #include "plan.hpp"
 #include "scan.hpp"
 
@@ -896,11 +897,14 @@ static int plan_build(spblas_gfx950_handle_t h, spblas_gfx950_plan_s* pl, int al
   hipStream_t s = h->stream;
   const O* rowptr = static_cast<const O*>(pl->rowptr);
   const int64_t m = pl->m, nnz = pl->nnz;
-  pl->win = pl->win_req > 0 ? pl->win_req
-                            : pl->value_type == SPBLAS_GFX950_F32 ? window_of<float>::value : window_of<double>::value;
+  // (complex values: the window of complex.hip, whose 2 * win products of 8 / 16 bytes fill the same LDS)
+  pl->win = pl->win_req > 0                         ? pl->win_req
+            : is_complex_type(pl->value_type)       ? complex_window(pl->value_type)
+            : pl->value_type == SPBLAS_GFX950_F32 ? window_of<float>::value
+                                                    : window_of<double>::value;
   pl->nwin = nnz / pl->win + 1;
   pl->vector_lpr = pick_lpr(m, nnz);
-  const size_t tsz = pl->value_type == SPBLAS_GFX950_F32 ? 4 : 8;
+  const size_t tsz = pl->value_type == SPBLAS_GFX950_F32 ? 4 : pl->value_type == SPBLAS_GFX950_C64 ? 16 : 8;
 
   int rc;
   unsigned long long* d_stats = nullptr;
@@ -1159,9 +1163,11 @@ int spblas_gfx950_spmv_plan_create(spblas_gfx950_handle_t handle, spblas_gfx950_
   if (offset_type == SPBLAS_GFX950_I32 && nnz > INT32_MAX)
     return SPBLAS_GFX950_STATUS_INVALID_SIZE;
   if ((offset_type != SPBLAS_GFX950_I32 && offset_type != SPBLAS_GFX950_I64) ||
-      (value_type != SPBLAS_GFX950_F32 && value_type != SPBLAS_GFX950_F64) || alg < 0 ||
+      (value_type != SPBLAS_GFX950_F32 && value_type != SPBLAS_GFX950_F64 && !is_complex_type(value_type)) || alg < 0 ||
       alg > SPBLAS_GFX950_SPMV_SLICED)
     return SPBLAS_GFX950_STATUS_INVALID_VALUE;
+  if (is_complex_type(value_type) && alg == SPBLAS_GFX950_SPMV_SLICED)  // (complex values: VECTOR / ROWBLOCK structures only)
+    return SPBLAS_GFX950_STATUS_NOT_SUPPORTED;
   if (!rowptr || (nnz > 0 && !colind))
     return SPBLAS_GFX950_STATUS_INVALID_POINTER;
   if (alg == SPBLAS_GFX950_SPMV_SLICED && nnz > 0 && !values)
@@ -1195,7 +1201,7 @@ int spblas_gfx950_spmv_plan_create(spblas_gfx950_handle_t handle, spblas_gfx950_
       pl->refresh_each_call = 0;
     if (rc == SPBLAS_GFX950_STATUS_SUCCESS)
       store_trial(handle, pl, values);
-  } else if (rc == SPBLAS_GFX950_STATUS_SUCCESS && alg == SPBLAS_GFX950_SPMV_AUTO && values &&
+  } else if (rc == SPBLAS_GFX950_STATUS_SUCCESS && alg == SPBLAS_GFX950_SPMV_AUTO && values && !is_complex_type(value_type) &&
              (handle->value_snapshot != 0 ||
               // (plain operands: large and NOT skewed -- a power-law matrix would get the hot-column split, whose refresh
               // gathers through two source maps: 6.9 against 3.4 ms for the row-block kernel at cfg4, after 50 ms of inspect)
@@ -1286,7 +1292,7 @@ int spblas_gfx950_spmv_plan_update_values(spblas_gfx950_handle_t handle, spblas_
     return SPBLAS_GFX950_STATUS_INVALID_HANDLE;
   if (!plan || !values)
     return SPBLAS_GFX950_STATUS_INVALID_POINTER;
-  if (plan->detached)  // (the source positions index arrays that are gone: inspect again)
+  if (plan->detached || is_complex_type(plan->value_type))  // (the source positions index arrays that are gone: inspect again)
     return SPBLAS_GFX950_STATUS_NOT_SUPPORTED;
   if (plan->alg != SPBLAS_GFX950_SPMV_SLICED)
     return SPBLAS_GFX950_STATUS_SUCCESS;  // other algorithms read the caller's values directly
@@ -1656,6 +1662,9 @@ int spblas_gfx950_spmv(spblas_gfx950_handle_t handle, spblas_gfx950_plan_t plan,
                        int64_t nnz, const void* alpha, const void* rowptr, const int32_t* colind,
                        const void* values, const void* x, const void* beta, void* y, int offset_type,
                        int value_type) {
+  if (is_complex_type(value_type))  // complex.hip, nothing conjugated
+    return spblas_gfx950_spmv_conj(handle, plan, op, m, n, nnz, alpha, rowptr, colind, values, x, beta, y, offset_type,
+                                   value_type, 0);
   if (!handle)
     return SPBLAS_GFX950_STATUS_INVALID_HANDLE;
   if (m < 0 || n < 0 || nnz < 0 || m > INT32_MAX || n > INT32_MAX)

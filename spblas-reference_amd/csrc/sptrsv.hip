@@ -28,6 +28,7 @@
 // Row sums are computed G lanes wide and tree-reduced, so they re-associate with respect to the
 // reference's sequential loop: parity is norm-wise, not bit-wise.
 #include "common.hpp"
+#include "complex_api.hpp"
 #include "scan.hpp"
 
 #include <algorithm>
@@ -985,6 +986,8 @@ int spblas_gfx950_sptrsv_status(spblas_gfx950_handle_t handle, spblas_gfx950_trs
 int spblas_gfx950_sptrsv_solve(spblas_gfx950_handle_t handle, spblas_gfx950_trsv_t plan, int64_t m, int64_t nnz,
                                const void* alpha, const int32_t* rowptr, const int32_t* colind, const void* values,
                                const void* b, void* x, int value_type) {
+  if (is_complex_type(value_type))  // complex values: SpMV / SpMM only (complex.hip)
+    return SPBLAS_GFX950_STATUS_NOT_SUPPORTED;
   if (!handle)
     return SPBLAS_GFX950_STATUS_INVALID_HANDLE;
   if (!plan || !alpha || !rowptr || (nnz > 0 && (!colind || !values)) || (m > 0 && (!b || !x)))

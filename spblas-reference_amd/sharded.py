@@ -67,6 +67,12 @@ def _order_before_collective(group, tensor):
         torch.cuda.synchronize()
 
 
+def _real_values_only(vals, what):
+    """The multi-GPU paths take float32 / float64 values (complex values: single-GPU SpMV / SpMM only)."""
+    if vals is not None and vals.dtype.is_complex:
+        raise TypeError(f"{what}: complex values are supported for single-GPU SpMV / SpMM only, got {vals.dtype}")
+
+
 class ShardedSpMV:
     """y = A x with A row-sharded over the ranks of `group`.
 
@@ -84,6 +90,7 @@ class ShardedSpMV:
     """
 
     def __init__(self, a_local, bounds, group=None, local_spmv=None, inspect=True, gather="auto", alg=None):
+        _real_values_only(a_local.values(), "ShardedSpMV")
         self.group = group
         self.rank = dist.get_rank(group) if dist.is_initialized() else 0
         self.world = dist.get_world_size(group) if dist.is_initialized() else 1
@@ -182,6 +189,7 @@ class PipelinedShardedSpMV:
     reduce (spmv_sliced.hip) keeps the chip full on the small stripes."""
 
     def __init__(self, a_chunks, ranges, group=None, local_spmv=None, inspect=True, alg=None):
+        _real_values_only(a_chunks[0].values(), "PipelinedShardedSpMV")
         self.group = group
         self.rank = dist.get_rank(group) if dist.is_initialized() else 0
         self.world = dist.get_world_size(group) if dist.is_initialized() else 1
@@ -268,6 +276,7 @@ class OverlappedShardedSpMV:
     (CPU gloo tests): it returns (expand, reduce) with reduce(c, y_stripe_local)."""
 
     def __init__(self, a_local, ranges, group=None, stages=None, alg=None):
+        _real_values_only(a_local.values(), "OverlappedShardedSpMV")
         self.group = group
         self.rank = dist.get_rank(group) if dist.is_initialized() else 0
         self.world = dist.get_world_size(group) if dist.is_initialized() else 1
@@ -399,6 +408,7 @@ class FusedShardedSpMV:
         chunks > 0 prepares step_dependent(): the dependent iteration whose peer rows arrive chunk by chunk behind the next
         expand (spblas_gfx950_spmv_step_bcast_chunked); shared_device: several ranks run on ONE device (tests, bench.py
         --debug-one-gpu) -- their waiting expands are kept to a fraction of the device so that they cannot starve each other."""
+        _real_values_only(a_local.values(), "FusedShardedSpMV")
         import ctypes
         if not (dist.is_available() and dist.is_initialized()):
             raise RuntimeError("FusedShardedSpMV needs an initialised process group")
@@ -729,6 +739,7 @@ class ShardedSpMM:
     (one all-gather of the row blocks, in place for equal shards, direct sends for nnz-balanced ones)."""
 
     def __init__(self, a_local, bounds, ncols, group=None, local_spmm=None, inspect=True):
+        _real_values_only(a_local.values(), "ShardedSpMM")
         self.group = group
         self.rank = dist.get_rank(group) if dist.is_initialized() else 0
         self.world = dist.get_world_size(group) if dist.is_initialized() else 1
