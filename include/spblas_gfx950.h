@@ -78,7 +78,16 @@ typedef enum spblas_gfx950_datatype {
    * for them, before any other check; so do plan_update_values / plan_detach and the two-stage / multi-GPU calls on a
    * complex plan. */
   SPBLAS_GFX950_C32 = 2, /* std::complex<float>  */
-  SPBLAS_GFX950_C64 = 3  /* std::complex<double> */
+  SPBLAS_GFX950_C64 = 3, /* std::complex<double> */
+  /* 16-bit values; alpha / beta point at ONE float each.  Products and sums are formed in fp32 and every output element is
+   * rounded to the 16-bit type once (round-to-nearest-even; beta * y is added in fp32 before that rounding).  SpMV (op N)
+   * and SpMM on CSR with int32 columns only: spmv_plan_create (AUTO / VECTOR / ROWBLOCK; AUTO never picks SLICED, SLICED
+   * returns STATUS_NOT_SUPPORTED), spblas_gfx950_spmv, spblas_gfx950_spmm[_strided], spmm_inspect.  op = T, the _conj entry
+   * points and every other entry point that takes a value type (spgemm_numeric[_addend], csr_add_numeric, csr_transpose,
+   * scale, sptrsv_solve) return STATUS_NOT_SUPPORTED for them, before any other check; so do plan_update_values /
+   * plan_detach / spmv_expand / spmv_reduce_rows on a 16-bit plan. */
+  SPBLAS_GFX950_F16 = 4, /* IEEE binary16 (torch.float16) */
+  SPBLAS_GFX950_BF16 = 5 /* bfloat16 (torch.bfloat16)     */
 } spblas_gfx950_datatype;
 
 typedef enum spblas_gfx950_indextype {

@@ -24,7 +24,7 @@ HIP_ERROR = 7
 INSUFFICIENT_SPACE = 8
 PLAN_MISMATCH = 9
 
-F32, F64, C32, C64 = 0, 1, 2, 3
+F32, F64, C32, C64, F16, BF16 = 0, 1, 2, 3, 4, 5
 CONJ_A, CONJ_X = 1, 2  # conj_flags bits of spblas_gfx950_spmv_conj / spblas_gfx950_spmm_strided_conj
 I32, I64 = 0, 1
 OP_N, OP_T = 0, 1

@@ -31,6 +31,13 @@ matrix_opt).  Complex operands may be conjugated -- conjugated(A), conjugated(x 
 conjugated iff an odd number of conjugated views wrap it (conjugated(scaled(s, A)) = conj(s) conj(A)).  Everything else with
 complex values -- csc_view / transposed() operands, int64 column indices, SpGEMM, add, transpose, scale, triangular_solve --
 raises TypeError; an output with the conj bit set raises ValueError.
+
+16-bit values: float16 / bfloat16 for SpMV and SpMM on a csr_view with int32 column indices (int32 / int64 row offsets),
+plan-free or inspected (VECTOR / ROWBLOCK / AUTO plans, matrix_opt), scaled() by real factors.  A, x / B and y / C share the
+one 16-bit type; products and sums are formed in fp32 and every output element is rounded once.  Everything else with 16-bit
+values -- csc_view / transposed() operands, int64 column indices, mixed value types, a complex scaled() factor, conjugated
+views, SpGEMM, add, transpose, scale, triangular_solve, the multi-GPU classes -- raises TypeError (conjugated views:
+RuntimeError, as for real operands).
 """
 import ctypes
 import threading
@@ -477,8 +484,10 @@ class c_complex128(_c_complex):
 
 
 _VT = {torch.float32: (_capi.F32, ctypes.c_float), torch.float64: (_capi.F64, ctypes.c_double),
-       torch.complex64: (_capi.C32, c_complex64), torch.complex128: (_capi.C64, c_complex128)}
+       torch.complex64: (_capi.C32, c_complex64), torch.complex128: (_capi.C64, c_complex128),
+       torch.float16: (_capi.F16, ctypes.c_float), torch.bfloat16: (_capi.BF16, ctypes.c_float)}
 _COMPLEX = (torch.complex64, torch.complex128)
+_LOWP = (torch.float16, torch.bfloat16)  # alpha / beta of a 16-bit call are float (fp32) scalars
 _OT = {torch.int32: _capi.I32, torch.int64: _capi.I64}
 
 
@@ -487,13 +496,106 @@ def _ptr(t):
         t.data_ptr() if t is not None else 0)
 
 
-def _vtype(t, what, complex_ok=False):
+def _vtype(t, what, complex_ok=False, lowp_ok=False):
     if t.dtype in _COMPLEX and not complex_ok:
         raise TypeError(f"{what}: complex values are supported for SpMV / SpMM on csr_view operands only, got {t.dtype}")
+    if t.dtype in _LOWP and not lowp_ok:
+        raise TypeError(f"{what}: {t.dtype} values are supported for SpMV / SpMM on csr_view operands only")
     if t.dtype not in _VT:
-        raise TypeError(f"{what}: gfx950 backend supports float32/float64 values (complex64/complex128 for SpMV / SpMM), "
-                        f"got {t.dtype}")
+        raise TypeError(f"{what}: gfx950 backend supports float32/float64 values (complex64/complex128, float16/bfloat16 "
+                        f"for SpMV / SpMM), got {t.dtype}")
     return _VT[t.dtype]
+
+
+def _lowp_dtype(t):
+    """The 16-bit value type of an operand (a view's values or a dense tensor), else None."""
+    base = get_ultimate_base(t)
+    vals = base if _is_tensor(base) else (base.values() if hasattr(base, "values") else None)
+    return vals.dtype if vals is not None and vals.dtype in _LOWP else None
+
+
+def _reject_lowp(what, *ts):
+    for t in ts:
+        dt = _lowp_dtype(t) if t is not None else None
+        if dt is not None:
+            raise TypeError(f"{what}: {dt} values are supported for SpMV / SpMM on csr_view operands only")
+
+
+def _lowp_operand(a, what):
+    """The csr_view under a 16-bit operand; TypeError for everything out of scope."""
+    a_base = get_ultimate_base(a)
+    dt = _lowp_dtype(a) or "16-bit"
+    if not isinstance(a_base, csr_view):
+        raise TypeError(f"{what}: {dt} values take a csr_view operand (csc_view / transposed(): not supported)")
+    if a_base.values() is None or a_base.values().dtype not in _LOWP:
+        raise TypeError(f"{what}: A, x / B and y / C must share one 16-bit value type, got A of "
+                        f"{None if a_base.values() is None else a_base.values().dtype}")
+    if a_base.colind() is not None and a_base.colind().dtype != torch.int32:
+        raise TypeError(f"{what}: {dt} values take int32 column indices only")
+    _check_csr(a_base, what)
+    return a_base
+
+
+def _lowp_alpha(a, b):
+    """alpha of a 16-bit call: the product of the scaled() factors, real only (a float scalar)."""
+    f = get_scaling_factor(a, b)
+    if f is None:
+        return 1.0
+    if isinstance(f, complex) or (_is_tensor(f) and f.is_complex()):
+        raise TypeError(f"multiply: {_lowp_dtype(a) or _lowp_dtype(b)} operands take real scaled() factors only, got the "
+                        f"complex factor {f}")
+    return float(f)
+
+
+def _spmv_lowp(info, a, b, c, prepare_only):
+    """_spmv for float16 / bfloat16 operands (spblas_gfx950_spmv, lowp.hip)."""
+    a_base, b_base = _lowp_operand(a, "multiply"), get_ultimate_base(b)
+    _reject_conjugated(a, b, c)
+    if not _is_tensor(c) or c.dim() != 1:
+        raise TypeError("multiply: the output vector must be a plain 1-D device tensor")
+    dt = a_base.values().dtype
+    if b_base.dtype != dt or c.dtype != dt:
+        raise TypeError(f"multiply: A, x and y must share one value type, got {dt}, {b_base.dtype}, {c.dtype}")
+    if a_base.shape()[0] != c.shape[0] or a_base.shape()[1] != b_base.shape[0]:
+        raise ValueError("multiply: matrix and vector dimensions are incompatible.")
+    if not (b_base.is_contiguous() and c.is_contiguous()):
+        raise ValueError("multiply: x and y must be contiguous")
+    vt, ct = _vtype(a_base.values(), "multiply", lowp_ok=True)
+    alpha, beta = ct(_lowp_alpha(a, b)), ct(0)
+    hd = _Handle.current(c.device)
+    plan = _find_plan(info, a, a_base)
+    m, n = a_base.shape()
+    args = (hd.h, plan.plan if plan else None, _capi.OP_N, m, n, a_base.size(), ctypes.byref(alpha), _ptr(a_base.rowptr()),
+            _ptr(a_base.colind()), _ptr(a_base.values()), _ptr(b_base), ctypes.byref(beta), _ptr(c),
+            _OT[a_base.rowptr().dtype], vt)
+    if prepare_only:  # (the entry point with its bound arguments, and what keeps the operands alive)
+        return (_capi.lib().spblas_gfx950_spmv, args), (alpha, beta, plan, a, b, c)
+    check(_capi.lib().spblas_gfx950_spmv(*args), "multiply")
+
+
+def _spmm_lowp(info, a, b, c):
+    """_spmm for float16 / bfloat16 operands (spblas_gfx950_spmm_strided, lowp.hip)."""
+    a_base, b_base = _lowp_operand(a, "multiply"), get_ultimate_base(b)
+    _reject_conjugated(a, b, c)
+    if not _is_tensor(c) or c.dim() != 2:
+        raise TypeError("multiply: the output matrix must be a plain 2-D device tensor")
+    dt = a_base.values().dtype
+    if b_base.dtype != dt or c.dtype != dt:
+        raise TypeError(f"multiply: A, B and C must share one value type, got {dt}, {b_base.dtype}, {c.dtype}")
+    if (a_base.shape()[0] != c.shape[0] or b_base.shape[1] != c.shape[1]
+            or a_base.shape()[1] != b_base.shape[0]):
+        raise ValueError("multiply: matrix dimensions are incompatible.")
+    vt, ct = _vtype(a_base.values(), "multiply", lowp_ok=True)
+    m, k = a_base.shape()
+    n = c.shape[1]
+    (brs, bcs), (crs, ccs) = _dense_strides(b_base, k, n), _dense_strides(c, m, n)
+    alpha, beta = ct(_lowp_alpha(a, b)), ct(0)
+    plan = _find_plan(info, a, a_base)
+    hd = _Handle.current(c.device)
+    check(_capi.lib().spblas_gfx950_spmm_strided(hd.h, plan.plan if plan is not None else None, m, k, n, a_base.size(),
+                                                 ctypes.byref(alpha), _ptr(a_base.rowptr()), _ptr(a_base.colind()),
+                                                 _ptr(a_base.values()), _ptr(b_base), brs, bcs, ctypes.byref(beta), _ptr(c),
+                                                 crs, ccs, _OT[a_base.rowptr().dtype], vt), "multiply")
 
 
 def _is_complex_view(t):
@@ -626,6 +728,8 @@ def _int32_columns(a, what):
         return a
     if a.values() is not None and a.values().dtype in _COMPLEX:
         raise TypeError(f"{what}: complex values take int32 column indices only")
+    if a.values() is not None and a.values().dtype in _LOWP:
+        raise TypeError(f"{what}: {a.values().dtype} values take int32 column indices only")
     hit = _NARROWED.get(id(idx))
     if hit is None or hit[0] is not idx:
         bound = a.shape()[1] if csr else a.shape()[0]
@@ -669,7 +773,7 @@ def _build_plan(a_base, alg=_capi.SPMV_AUTO, snapshot=0):
     """snapshot: the value of SPBLAS_GFX950_OPT_VALUE_SNAPSHOT -- 1 / True: AUTO may choose the plan that keeps a re-tiled
     copy of the values (matrix_opt operands); 2: and the plan keeps its source positions from the start."""
     hd = _Handle.current(a_base.rowptr().device)
-    vt, _ = _vtype(a_base.values(), "multiply_inspect", complex_ok=True)
+    vt, _ = _vtype(a_base.values(), "multiply_inspect", complex_ok=True, lowp_ok=True)
     plan = ctypes.c_void_p()
     m, n = a_base.shape()
     hd.set_option(_capi.OPT_VALUE_SNAPSHOT, int(snapshot))
@@ -766,6 +870,7 @@ def transpose(*args):
     of every output row in source order exactly like the reference's counting sort
     (algorithms/transpose_impl.hpp:14-53).  b's arrays are caller-allocated."""
     a, b = args[-2], args[-1]
+    _reject_lowp("transpose", a, b)
     if not (isinstance(a, csr_view) and isinstance(b, csr_view)):
         raise TypeError("transpose: csr_view operands")
     if a.shape()[0] != b.shape()[1] or a.shape()[1] != b.shape()[0]:
@@ -824,6 +929,8 @@ def _find_plan(info, a, a_base):
 def _spmv(info, a, b, c, prepare_only=False):
     if _is_complex_view(a) or _is_complex_view(b):
         return _spmv_complex(info, a, b, c, prepare_only)
+    if _lowp_dtype(a) or _lowp_dtype(b):
+        return _spmv_lowp(info, a, b, c, prepare_only)
     a_base, b_base = get_ultimate_base(a), get_ultimate_base(b)
     a_base = _int32_columns(a_base, "multiply")
     _reject_conjugated(a, b, c)
@@ -903,6 +1010,8 @@ class prepared_multiply:
 def _spmm(info, a, b, c):
     if _is_complex_view(a) or _is_complex_view(b):
         return _spmm_complex(info, a, b, c)
+    if _lowp_dtype(a) or _lowp_dtype(b):
+        return _spmm_lowp(info, a, b, c)
     a_base, b_base = get_ultimate_base(a), get_ultimate_base(b)
     a_base = _int32_columns(a_base, "multiply")
     _reject_conjugated(a, b, c)
@@ -998,6 +1107,9 @@ def multiply_inspect(*args, alg=_capi.SPMV_AUTO, values_will_change=False):
     a_base = get_ultimate_base(a)
     if _is_complex_view(a) and not _is_sparse(b):  # conjugated complex operands are taken (csr_view only)
         a_base = _complex_operand(a, "multiply_inspect")
+    elif _lowp_dtype(a) and not _is_sparse(b):  # 16-bit: csr_view with int32 columns only
+        a_base = _lowp_operand(a, "multiply_inspect")
+        _reject_conjugated(a, b, c)
     else:
         _reject_conjugated(a, b, c)
     if isinstance(a_base, (csr_view, csc_view)) and not _is_sparse(b) and a_base.values() is not None:
@@ -1056,6 +1168,7 @@ def _spgemm_operands(a, b, c, d=None):
     Returns (a_eff, b_eff, c_eff, d_eff)."""
     a_base, b_base = get_ultimate_base(a), get_ultimate_base(b)
     _reject_complex("multiply_compute", a, b, c, d)
+    _reject_lowp("multiply_compute", a, b, c, d)
     if not isinstance(c, (csr_view, csc_view)):
         raise NotImplementedError("gfx950 SpGEMM result must be a csr_view or csc_view")
     _reject_conjugated(a, b)
@@ -1211,6 +1324,7 @@ def multiply_numeric(state, a, b, c, d=None):
 def _add_operands(a, b, c):
     a_base, b_base = get_ultimate_base(a), get_ultimate_base(b)
     _reject_complex("add", a, b, c)
+    _reject_lowp("add", a, b, c)
     if not (isinstance(a_base, csr_view) and isinstance(b_base, csr_view) and isinstance(c, csr_view)):
         raise NotImplementedError("gfx950 add supports CSR + CSR -> CSR")
     _reject_conjugated(a, b)
@@ -1342,6 +1456,7 @@ class _TrsvPlan:
 def _trsv_operands(a, uplo, diag, b, x):
     a_base = get_ultimate_base(a)
     _reject_complex("triangular_solve", a, b, x)
+    _reject_lowp("triangular_solve", a, b, x)
     if not isinstance(a_base, csr_view):
         raise NotImplementedError("gfx950 triangular_solve supports csr_view operands")
     _reject_conjugated(a, b, x)

@@ -20,6 +20,7 @@
 // The real kernels (spmv.hip, spmm.hip) are untouched; this file only adds code.
 #include "common.hpp"
 #include "complex_api.hpp"
+#include "lowp_api.hpp"
 #include "plan.hpp"
 
 namespace spb {
@@ -765,6 +766,8 @@ extern "C" int spblas_gfx950_spmv_conj(spblas_gfx950_handle_t handle, spblas_gfx
                                        int64_t nnz, const void* alpha, const void* rowptr, const int32_t* colind,
                                        const void* values, const void* x, const void* beta, void* y, int offset_type,
                                        int value_type, int conj_flags) {
+  if (is_lowp_type(value_type))  // (16-bit values: spblas_gfx950_spmv)
+    return SPBLAS_GFX950_STATUS_NOT_SUPPORTED;
   if (conj_flags < 0 || conj_flags > 3)
     return SPBLAS_GFX950_STATUS_INVALID_VALUE;
   if (!is_complex_type(value_type)) {
@@ -802,6 +805,8 @@ extern "C" int spblas_gfx950_spmm_strided_conj(spblas_gfx950_handle_t handle, sp
                                                const int32_t* colind, const void* values, const void* B, int64_t brs,
                                                int64_t bcs, const void* beta, void* C, int64_t crs, int64_t ccs,
                                                int offset_type, int value_type, int conj_flags) {
+  if (is_lowp_type(value_type))  // (16-bit values: spblas_gfx950_spmm_strided)
+    return SPBLAS_GFX950_STATUS_NOT_SUPPORTED;
   if (conj_flags < 0 || conj_flags > 3)
     return SPBLAS_GFX950_STATUS_INVALID_VALUE;
   if (!is_complex_type(value_type)) {

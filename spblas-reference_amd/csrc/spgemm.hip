@@ -29,6 +29,7 @@
 // symbolic pass, add_compute the numeric one; columns come out ascending like the CPU SPA + sort.
 #include "common.hpp"
 #include "complex_api.hpp"
+#include "lowp_api.hpp"
 #include <type_traits>
 #include "scan.hpp"
 
@@ -2138,7 +2139,7 @@ int spblas_gfx950_spgemm_numeric(spblas_gfx950_handle_t handle, spblas_gfx950_sp
                                  const int32_t* b_rowptr, const int32_t* b_colind, const void* b_values,
                                  int32_t* c_rowptr, int32_t* c_colind, void* c_values, int64_t c_capacity,
                                  int value_type) {
-  if (is_complex_type(value_type))  // complex values: SpMV / SpMM only (complex.hip)
+  if (is_complex_type(value_type) || is_lowp_type(value_type))  // complex / 16-bit values: SpMV / SpMM only
     return SPBLAS_GFX950_STATUS_NOT_SUPPORTED;
   return spgemm_numeric_impl(handle, st, alpha, a_rowptr, a_colind, a_values, b_rowptr, b_colind, b_values, nullptr,
                              nullptr, nullptr, nullptr, c_rowptr, c_colind, c_values, c_capacity, value_type);
@@ -2150,7 +2151,7 @@ int spblas_gfx950_spgemm_numeric_addend(spblas_gfx950_handle_t handle, spblas_gf
                                         const void* beta, const int32_t* d_rowptr, const int32_t* d_colind,
                                         const void* d_values, int32_t* c_rowptr, int32_t* c_colind, void* c_values,
                                         int64_t c_capacity, int value_type) {
-  if (is_complex_type(value_type))  // complex values: SpMV / SpMM only (complex.hip)
+  if (is_complex_type(value_type) || is_lowp_type(value_type))  // complex / 16-bit values: SpMV / SpMM only
     return SPBLAS_GFX950_STATUS_NOT_SUPPORTED;
   if (!d_rowptr)
     return SPBLAS_GFX950_STATUS_INVALID_POINTER;
@@ -2179,7 +2180,7 @@ int spblas_gfx950_csr_add_numeric(spblas_gfx950_handle_t handle, spblas_gfx950_s
                                   const void* beta, const int32_t* b_rowptr, const int32_t* b_colind,
                                   const void* b_values, int32_t* c_rowptr, int32_t* c_colind, void* c_values,
                                   int64_t c_capacity, int value_type) {
-  if (is_complex_type(value_type))  // complex values: SpMV / SpMM only (complex.hip)
+  if (is_complex_type(value_type) || is_lowp_type(value_type))  // complex / 16-bit values: SpMV / SpMM only
     return SPBLAS_GFX950_STATUS_NOT_SUPPORTED;
   if (!b_rowptr)
     return SPBLAS_GFX950_STATUS_INVALID_POINTER;

@@ -25,6 +25,7 @@
 // Algorithmic bytes = nnz*(sizeof(T)+4) + (m+1)*sizeof(O) + (k*n + m*n)*sizeof(T).
 #include "common.hpp"
 #include "complex_api.hpp"
+#include "lowp_api.hpp"
 #include "plan.hpp"
 #include "scan.hpp"
 
@@ -1281,6 +1282,9 @@ extern "C" int spblas_gfx950_spmm(spblas_gfx950_handle_t handle, spblas_gfx950_p
   if (is_complex_type(value_type))  // complex.hip, nothing conjugated (layout_right with leading dimensions ldb / ldc)
     return spblas_gfx950_spmm_strided_conj(handle, plan, m, k, n, nnz, alpha, rowptr, colind, values, B, ldb, 1, beta, C, ldc, 1,
                                            offset_type, value_type, 0);
+  if (is_lowp_type(value_type))  // lowp.hip (layout_right with leading dimensions ldb / ldc)
+    return lowp_spmm_strided(handle, plan, m, k, n, nnz, alpha, rowptr, colind, values, B, ldb, 1, beta, C, ldc, 1, offset_type,
+                             value_type);
   if (!handle)
     return SPBLAS_GFX950_STATUS_INVALID_HANDLE;
   if (m < 0 || k < 0 || n < 0 || nnz < 0 || m > INT32_MAX || k > INT32_MAX || ldb < n || ldc < n)
@@ -1317,6 +1321,9 @@ extern "C" int spblas_gfx950_spmm_strided(spblas_gfx950_handle_t handle, spblas_
   if (is_complex_type(value_type))
     return spblas_gfx950_spmm_strided_conj(handle, plan, m, k, n, nnz, alpha, rowptr, colind, values, B, brs, bcs, beta, C, crs,
                                            ccs, offset_type, value_type, 0);
+  if (is_lowp_type(value_type))
+    return lowp_spmm_strided(handle, plan, m, k, n, nnz, alpha, rowptr, colind, values, B, brs, bcs, beta, C, crs, ccs,
+                             offset_type, value_type);
   if (bcs == 1 && ccs == 1) {  // both layout_right: the regular kernels, plan included
     // (a layout_left mdspan with ONE row also has strides (1, 1): its row stride says nothing -- an operand of at most one
     // row gets the leading dimension the regular entry point asks for; round-4 advisor finding)

@@ -16,6 +16,7 @@
 //   spmv_transpose_kernel  op = T (CSC / transposed(csr)): scatter with HW float atomics.
 #include "common.hpp"
 #include "complex_api.hpp"
+#include "lowp_api.hpp"
 #include "plan.hpp"
 #include "scan.hpp"
 
@@ -897,14 +898,19 @@ static int plan_build(spblas_gfx950_handle_t h, spblas_gfx950_plan_s* pl, int al
   hipStream_t s = h->stream;
   const O* rowptr = static_cast<const O*>(pl->rowptr);
   const int64_t m = pl->m, nnz = pl->nnz;
-  // (complex values: the window of complex.hip, whose 2 * win products of 8 / 16 bytes fill the same LDS)
+  // (complex values: the window of complex.hip, whose 2 * win products of 8 / 16 bytes fill the same LDS; 16-bit values: that
+  // of lowp.hip, whose products are fp32)
   pl->win = pl->win_req > 0                         ? pl->win_req
             : is_complex_type(pl->value_type)       ? complex_window(pl->value_type)
+            : is_lowp_type(pl->value_type)          ? lowp_window()
             : pl->value_type == SPBLAS_GFX950_F32 ? window_of<float>::value
                                                     : window_of<double>::value;
   pl->nwin = nnz / pl->win + 1;
   pl->vector_lpr = pick_lpr(m, nnz);
-  const size_t tsz = pl->value_type == SPBLAS_GFX950_F32 ? 4 : pl->value_type == SPBLAS_GFX950_C64 ? 16 : 8;
+  // (bytes of one long-row partial: 16-bit values keep theirs in fp32)
+  const size_t tsz = pl->value_type == SPBLAS_GFX950_F32 || is_lowp_type(pl->value_type) ? 4
+                     : pl->value_type == SPBLAS_GFX950_C64                                 ? 16
+                                                                                           : 8;
 
   int rc;
   unsigned long long* d_stats = nullptr;
@@ -1163,10 +1169,12 @@ int spblas_gfx950_spmv_plan_create(spblas_gfx950_handle_t handle, spblas_gfx950_
   if (offset_type == SPBLAS_GFX950_I32 && nnz > INT32_MAX)
     return SPBLAS_GFX950_STATUS_INVALID_SIZE;
   if ((offset_type != SPBLAS_GFX950_I32 && offset_type != SPBLAS_GFX950_I64) ||
-      (value_type != SPBLAS_GFX950_F32 && value_type != SPBLAS_GFX950_F64 && !is_complex_type(value_type)) || alg < 0 ||
-      alg > SPBLAS_GFX950_SPMV_SLICED)
+      (value_type != SPBLAS_GFX950_F32 && value_type != SPBLAS_GFX950_F64 && !is_complex_type(value_type) &&
+       !is_lowp_type(value_type)) ||
+      alg < 0 || alg > SPBLAS_GFX950_SPMV_SLICED)
     return SPBLAS_GFX950_STATUS_INVALID_VALUE;
-  if (is_complex_type(value_type) && alg == SPBLAS_GFX950_SPMV_SLICED)  // (complex values: VECTOR / ROWBLOCK structures only)
+  // (complex and 16-bit values: VECTOR / ROWBLOCK structures only)
+  if ((is_complex_type(value_type) || is_lowp_type(value_type)) && alg == SPBLAS_GFX950_SPMV_SLICED)
     return SPBLAS_GFX950_STATUS_NOT_SUPPORTED;
   if (!rowptr || (nnz > 0 && !colind))
     return SPBLAS_GFX950_STATUS_INVALID_POINTER;
@@ -1202,6 +1210,7 @@ int spblas_gfx950_spmv_plan_create(spblas_gfx950_handle_t handle, spblas_gfx950_
     if (rc == SPBLAS_GFX950_STATUS_SUCCESS)
       store_trial(handle, pl, values);
   } else if (rc == SPBLAS_GFX950_STATUS_SUCCESS && alg == SPBLAS_GFX950_SPMV_AUTO && values && !is_complex_type(value_type) &&
+             !is_lowp_type(value_type) &&
              (handle->value_snapshot != 0 ||
               // (plain operands: large and NOT skewed -- a power-law matrix would get the hot-column split, whose refresh
               // gathers through two source maps: 6.9 against 3.4 ms for the row-block kernel at cfg4, after 50 ms of inspect)
@@ -1268,6 +1277,8 @@ int spblas_gfx950_spmv_plan_create(spblas_gfx950_handle_t handle, spblas_gfx950_
 }
 
 int spblas_gfx950_spmv_plan_detach(spblas_gfx950_handle_t handle, spblas_gfx950_plan_t plan) {
+  if (plan && is_lowp_type(plan->value_type))  // (16-bit plans hold no values: nothing to detach from)
+    return SPBLAS_GFX950_STATUS_NOT_SUPPORTED;
   if (!handle)
     return SPBLAS_GFX950_STATUS_INVALID_HANDLE;
   if (!plan)
@@ -1288,6 +1299,8 @@ int spblas_gfx950_spmv_plan_detach(spblas_gfx950_handle_t handle, spblas_gfx950_
 
 int spblas_gfx950_spmv_plan_update_values(spblas_gfx950_handle_t handle, spblas_gfx950_plan_t plan,
                                           const void* values) {
+  if (plan && is_lowp_type(plan->value_type))  // (16-bit plans: VECTOR / ROWBLOCK, which hold no values)
+    return SPBLAS_GFX950_STATUS_NOT_SUPPORTED;
   if (!handle)
     return SPBLAS_GFX950_STATUS_INVALID_HANDLE;
   if (!plan || !values)
@@ -1300,6 +1313,8 @@ int spblas_gfx950_spmv_plan_update_values(spblas_gfx950_handle_t handle, spblas_
 }
 
 int spblas_gfx950_spmv_expand(spblas_gfx950_handle_t handle, spblas_gfx950_plan_t plan, const void* x) {
+  if (plan && is_lowp_type(plan->value_type))  // (the two-stage form needs a SLICED plan, which 16-bit values never get)
+    return SPBLAS_GFX950_STATUS_NOT_SUPPORTED;
   if (!handle)
     return SPBLAS_GFX950_STATUS_INVALID_HANDLE;
   if (!plan || !x)
@@ -1313,6 +1328,8 @@ int spblas_gfx950_spmv_expand(spblas_gfx950_handle_t handle, spblas_gfx950_plan_
 
 int spblas_gfx950_spmv_reduce_rows(spblas_gfx950_handle_t handle, spblas_gfx950_plan_t plan, const void* alpha,
                                    const void* beta, void* y, int64_t row_begin, int64_t row_end) {
+  if (plan && is_lowp_type(plan->value_type))
+    return SPBLAS_GFX950_STATUS_NOT_SUPPORTED;
   if (!handle)
     return SPBLAS_GFX950_STATUS_INVALID_HANDLE;
   if (!plan || !alpha || !beta || !y)
@@ -1665,6 +1682,8 @@ int spblas_gfx950_spmv(spblas_gfx950_handle_t handle, spblas_gfx950_plan_t plan,
   if (is_complex_type(value_type))  // complex.hip, nothing conjugated
     return spblas_gfx950_spmv_conj(handle, plan, op, m, n, nnz, alpha, rowptr, colind, values, x, beta, y, offset_type,
                                    value_type, 0);
+  if (is_lowp_type(value_type))  // lowp.hip (op = T: STATUS_NOT_SUPPORTED)
+    return lowp_spmv(handle, plan, op, m, n, nnz, alpha, rowptr, colind, values, x, beta, y, offset_type, value_type);
   if (!handle)
     return SPBLAS_GFX950_STATUS_INVALID_HANDLE;
   if (m < 0 || n < 0 || nnz < 0 || m > INT32_MAX || n > INT32_MAX)

@@ -29,6 +29,7 @@
 // reference's sequential loop: parity is norm-wise, not bit-wise.
 #include "common.hpp"
 #include "complex_api.hpp"
+#include "lowp_api.hpp"
 #include "scan.hpp"
 
 #include <algorithm>
@@ -986,7 +987,7 @@ int spblas_gfx950_sptrsv_status(spblas_gfx950_handle_t handle, spblas_gfx950_trs
 int spblas_gfx950_sptrsv_solve(spblas_gfx950_handle_t handle, spblas_gfx950_trsv_t plan, int64_t m, int64_t nnz,
                                const void* alpha, const int32_t* rowptr, const int32_t* colind, const void* values,
                                const void* b, void* x, int value_type) {
-  if (is_complex_type(value_type))  // complex values: SpMV / SpMM only (complex.hip)
+  if (is_complex_type(value_type) || is_lowp_type(value_type))  // complex / 16-bit values: SpMV / SpMM only
     return SPBLAS_GFX950_STATUS_NOT_SUPPORTED;
   if (!handle)
     return SPBLAS_GFX950_STATUS_INVALID_HANDLE;

@@ -16,6 +16,7 @@
 
 #include "common.hpp"
 #include "complex_api.hpp"
+#include "lowp_api.hpp"
 #include "scan.hpp"
 
 namespace spb {
@@ -455,7 +456,7 @@ using namespace spb;
 extern "C" int spblas_gfx950_csr_transpose(spblas_gfx950_handle_t handle, int64_t m, int64_t n, int64_t nnz,
                                            const int32_t* rowptr, const int32_t* colind, const void* values,
                                            int32_t* t_rowptr, int32_t* t_colind, void* t_values, int value_type) {
-  if (is_complex_type(value_type))  // complex values: SpMV / SpMM only (complex.hip)
+  if (is_complex_type(value_type) || is_lowp_type(value_type))  // complex / 16-bit values: SpMV / SpMM only
     return SPBLAS_GFX950_STATUS_NOT_SUPPORTED;
   if (!handle)
     return SPBLAS_GFX950_STATUS_INVALID_HANDLE;
@@ -529,7 +530,7 @@ extern "C" int spblas_gfx950_narrow_indices(spblas_gfx950_handle_t handle, int64
 
 extern "C" int spblas_gfx950_scale(spblas_gfx950_handle_t handle, int64_t n, const void* alpha, void* values,
                                    int value_type) {
-  if (is_complex_type(value_type))  // complex values: SpMV / SpMM only (complex.hip)
+  if (is_complex_type(value_type) || is_lowp_type(value_type))  // complex / 16-bit values: SpMV / SpMM only
     return SPBLAS_GFX950_STATUS_NOT_SUPPORTED;
   if (!handle)
     return SPBLAS_GFX950_STATUS_INVALID_HANDLE;

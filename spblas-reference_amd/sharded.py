@@ -68,9 +68,11 @@ def _order_before_collective(group, tensor):
 
 
 def _real_values_only(vals, what):
-    """The multi-GPU paths take float32 / float64 values (complex values: single-GPU SpMV / SpMM only)."""
+    """The multi-GPU paths take float32 / float64 values (complex and 16-bit values: single-GPU SpMV / SpMM only)."""
     if vals is not None and vals.dtype.is_complex:
         raise TypeError(f"{what}: complex values are supported for single-GPU SpMV / SpMM only, got {vals.dtype}")
+    if vals is not None and vals.dtype in (torch.float16, torch.bfloat16):
+        raise TypeError(f"{what}: {vals.dtype} values are supported for single-GPU SpMV / SpMM only")
 
 
 class ShardedSpMV:
