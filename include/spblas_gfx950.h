@@ -245,7 +245,10 @@ int spblas_gfx950_plan_info_hot(spblas_gfx950_plan_t plan, int64_t info[8]);
  *                A plan of a row-skewed matrix that cuts its long rows into pieces (plan_info_sliced[8] > m or the
  *                plan was made without SPBLAS_GFX950_OPT_BIN_ROW_ALIGN on such a matrix) reduces all rows in ONE call:
  *                a proper sub-range returns STATUS_NOT_SUPPORTED there.  Plans created under OPT_BIN_ROW_ALIGN > 1 (what
- *                the striped multi-GPU step sets) never cut rows. */
+ *                the striped multi-GPU step sets) never cut rows.
+ * expand is not handed A's values: a plan that copies them on every multiply (a plain inspected csr_view below the size of
+ * value-free tiles) returns STATUS_NOT_SUPPORTED from it.  A VALUE-FREE plan is taken -- its expand gathers x only, and its
+ * reduce (spblas_gfx950_spmv_reduce_rows_bcast) reads the value array registered with the plan. */
 int spblas_gfx950_spmv_expand(spblas_gfx950_handle_t handle, spblas_gfx950_plan_t plan, const void* x);
 int spblas_gfx950_spmv_reduce_rows(spblas_gfx950_handle_t handle, spblas_gfx950_plan_t plan, const void* alpha,
                                    const void* beta, void* y, int64_t row_begin, int64_t row_end);

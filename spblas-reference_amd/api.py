@@ -41,6 +41,7 @@ RuntimeError, as for real operands).
 """
 import ctypes
 import threading
+import weakref
 
 import torch
 
@@ -713,14 +714,30 @@ def _dense_strides(t, rows, n):
     raise ValueError("multiply: dense operands must be row-major (layout_right) or column-major (layout_left)")
 
 
-_NARROWED = {}  # id of an int64 index tensor -> (the tensor, its int32 copy); a handful of entries, oldest dropped first
+# id of an int64 index tensor -> (weak reference to it, (its version, the range bound, the entry count) when narrowed, the copy)
+_NARROWED = {}
+_NARROWED_LOCK = threading.RLock()  # (re-entrant: a finaliser may run while this thread holds it)
+
+
+def _index_version(idx):
+    """torch's in-place edit counter of a tensor (copy_, idx[k] = v, any op with a trailing underscore bump it), or None for
+    a tensor that keeps none (made under inference mode): such an array is narrowed afresh on every call."""
+    try:
+        return idx._version
+    except RuntimeError:
+        return None
 
 
 def _int32_columns(a, what):
     """A csr_view / csc_view whose index array is int64 -- the slot this backend replaces admits them
     (vendor/rocsparse/types.hpp:16-24) -- as the same view over an int32 copy (spblas_gfx950_narrow_indices: ValueError if an
-    index does not fit the other dimension).  The copy is made once per index tensor and kept, so that multiply_inspect and
-    the multiplies that follow see ONE array (a plan is tied to its structure arrays); the kernels take int32 indices only.
+    index does not fit the other dimension).  The copy is made once per index tensor, version of its contents AND range
+    bound (the same tensor in a view with a smaller other dimension is checked against that one), so that
+    multiply_inspect and the multiplies that follow see ONE array (a plan is tied to its structure arrays) while a plan-free
+    multiply reads the caller's indices as they are at the time of the call: an in-place edit through torch is narrowed and
+    range-checked again (into a new copy: a plan built on the old one is no longer found, _check_index_version).  The
+    entry holds the source tensor weakly and goes away with it; the copy then lives on only inside a plan built on it.
+    The kernels take int32 indices only.
     SpMV and SpMM operands only (what the slot's type list admits and this backend does not)."""
     csr = isinstance(a, csr_view)
     idx = a.colind() if csr else a.rowind()
@@ -730,21 +747,55 @@ def _int32_columns(a, what):
         raise TypeError(f"{what}: complex values take int32 column indices only")
     if a.values() is not None and a.values().dtype in _LOWP:
         raise TypeError(f"{what}: {a.values().dtype} values take int32 column indices only")
-    hit = _NARROWED.get(id(idx))
-    if hit is None or hit[0] is not idx:
-        bound = a.shape()[1] if csr else a.shape()[0]
+    key, version = id(idx), _index_version(idx)
+    bound = int(a.shape()[1] if csr else a.shape()[0])     # what the copy was range-checked against is part of its identity
+    hit = _NARROWED.get(key)
+    if hit is None or hit[0]() is not idx or version is None or hit[1] != (version, bound, a.size()):
         dst = torch.empty(idx.numel(), dtype=torch.int32, device=idx.device)
         hd = _Handle.current(idx.device)
-        rc = _capi.lib().spblas_gfx950_narrow_indices(hd.h, a.size(), _ptr(idx), _ptr(dst), int(bound))
+        rc = _capi.lib().spblas_gfx950_narrow_indices(hd.h, a.size(), _ptr(idx), _ptr(dst), bound)
         if rc == _capi.INVALID_VALUE:
+            _NARROWED.pop(key, None)
             raise ValueError(f"{what}: a 64-bit index lies outside the matrix (or beyond 2^31 - 1)")
         check(rc, what)
-        while len(_NARROWED) >= 8:
-            _NARROWED.pop(next(iter(_NARROWED)))
-        hit = _NARROWED[id(idx)] = (idx, dst)
+
+        def forget(ref, key=key):
+            # (runs on whichever thread drops the last reference: the entry is removed only if it is still THIS tensor's)
+            with _NARROWED_LOCK:
+                if key in _NARROWED and _NARROWED[key][0] is ref:
+                    del _NARROWED[key]
+
+        with _NARROWED_LOCK:
+            hit = _NARROWED[key] = (weakref.ref(idx, forget), (version, bound, a.size()), dst)
     if csr:
-        return csr_view(a.values(), a.rowptr(), hit[1], a.shape(), a.size())
-    return csc_view(a.values(), a.colptr(), hit[1], a.shape(), a.size())
+        return csr_view(a.values(), a.rowptr(), hit[2], a.shape(), a.size())
+    return csc_view(a.values(), a.colptr(), hit[2], a.shape(), a.size())
+
+
+def _wide_indices(a_base):
+    idx = a_base.colind() if isinstance(a_base, csr_view) else a_base.rowind() if isinstance(a_base, csc_view) else None
+    return idx if idx is not None and idx.dtype == torch.int64 else None
+
+
+def _note_index_version(state, a_base):
+    """multiply_inspect on an operand with int64 indices: remember which contents of the index tensor the plan was built on."""
+    idx = _wide_indices(a_base)
+    if idx is not None and state is not None:
+        state.index_src = (weakref.ref(idx), _index_version(idx))
+
+
+def _check_index_version(info, a, a_base):
+    """The plan binds the structure (like the reference's inspect): int64 indices edited in place after multiply_inspect
+    are a user error, and one this layer can see -- it raises instead of multiplying with the old structure."""
+    idx = _wide_indices(a_base)
+    if idx is None:
+        return
+    mo = _get_matrix_opt(a)
+    for state in (info.state_ if info is not None else None, mo._plan if mo is not None else None):
+        src = getattr(state, "index_src", None)
+        if src is not None and src[0]() is idx and src[1] != _index_version(idx):
+            raise ValueError("multiply: the 64-bit index array was modified in place after multiply_inspect; "
+                             "inspect the matrix again (a plan is tied to the structure it was built on)")
 
 
 def _check_csr(a, what):
@@ -932,6 +983,7 @@ def _spmv(info, a, b, c, prepare_only=False):
     if _lowp_dtype(a) or _lowp_dtype(b):
         return _spmv_lowp(info, a, b, c, prepare_only)
     a_base, b_base = get_ultimate_base(a), get_ultimate_base(b)
+    _check_index_version(info, a, a_base)
     a_base = _int32_columns(a_base, "multiply")
     _reject_conjugated(a, b, c)
     if not _is_tensor(c) or c.dim() != 1:
@@ -978,7 +1030,8 @@ def _spmv(info, a, b, c, prepare_only=False):
                 _ptr(a_csr.colind()), _ptr(a_csr.values()), _ptr(b_base), ctypes.byref(beta), _ptr(c),
                 _OT[a_csr.rowptr().dtype], vt)
     if prepare_only:  # the entry point with its bound arguments; keep the operands alive with the bound call
-        return (_capi.lib().spblas_gfx950_spmv, args), (alpha, beta, plan, a, b, c)
+        # (a_csr: with int64 indices it holds the narrowed int32 copy the bound pointers refer to)
+        return (_capi.lib().spblas_gfx950_spmv, args), (alpha, beta, plan, a, b, c, a_csr)
     check(_capi.lib().spblas_gfx950_spmv(*args), "multiply")
 
 
@@ -1013,6 +1066,7 @@ def _spmm(info, a, b, c):
     if _lowp_dtype(a) or _lowp_dtype(b):
         return _spmm_lowp(info, a, b, c)
     a_base, b_base = get_ultimate_base(a), get_ultimate_base(b)
+    _check_index_version(info, a, a_base)
     a_base = _int32_columns(a_base, "multiply")
     _reject_conjugated(a, b, c)
     plan = None
@@ -1112,6 +1166,7 @@ def multiply_inspect(*args, alg=_capi.SPMV_AUTO, values_will_change=False):
         _reject_conjugated(a, b, c)
     else:
         _reject_conjugated(a, b, c)
+    wide_base = a_base
     if isinstance(a_base, (csr_view, csc_view)) and not _is_sparse(b) and a_base.values() is not None:
         a_base = _int32_columns(a_base, "multiply_inspect")
     if isinstance(a_base, csr_view) and not _is_sparse(b) and a_base.values() is not None:
@@ -1125,6 +1180,7 @@ def multiply_inspect(*args, alg=_capi.SPMV_AUTO, values_will_change=False):
         if is_spmm:
             plan.spmm_inspect()
         info.state_ = plan
+        _note_index_version(plan, wide_base)
         if mo is not None:
             mo._plan = plan
     elif isinstance(a_base, csc_view) and _is_tensor(get_ultimate_base(b)) and a_base.size() < 2 ** 31:
@@ -1132,6 +1188,7 @@ def multiply_inspect(*args, alg=_capi.SPMV_AUTO, values_will_change=False):
         info.state_ = _CscPlan(a_base, _capi.SPMV_ROWBLOCK if is_spmm else alg)
         if is_spmm:
             info.state_.plan.spmm_inspect()
+        _note_index_version(info.state_, wide_base)
     return info if ret else None
 
 

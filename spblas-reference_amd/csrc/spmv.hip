@@ -1319,7 +1319,9 @@ int spblas_gfx950_spmv_expand(spblas_gfx950_handle_t handle, spblas_gfx950_plan_
     return SPBLAS_GFX950_STATUS_INVALID_HANDLE;
   if (!plan || !x)
     return SPBLAS_GFX950_STATUS_INVALID_POINTER;
-  if (plan->alg != SPBLAS_GFX950_SPMV_SLICED || plan->refresh_each_call)  // (the two-stage form is not given A's values)
+  // (the two-stage form is not given A's values; a value-free plan needs none here -- its expand gathers x only, and its
+  // reduce reads the array registered with the plan, like spblas_gfx950_spmv_reduce_rows_bcast below)
+  if (plan->alg != SPBLAS_GFX950_SPMV_SLICED || (plan->refresh_each_call && !plan->vfree))
     return SPBLAS_GFX950_STATUS_NOT_SUPPORTED;
   if (plan->nnz == 0)
     return SPBLAS_GFX950_STATUS_SUCCESS;

@@ -3553,6 +3553,17 @@ static int sliced_reduce_typed(spblas_gfx950_handle_t h, spblas_gfx950_plan_s* p
       return rc;
     pl->s_partial_k = K;
   }
+  // fused multi-GPU step, throughput form: the wait for the PREVIOUS step's barrier goes right before the kernel that
+  // stores into the peers' copies of y -- everything before it overlaps the peers' stores still crossing the links.
+  // Every branch below that launches a peer-storing kernel calls it first (the value-free reduce as well as the tiled one).
+  auto wait_hook = [&]() -> int {
+    auto& bw = h->bcast_wait;
+    if (!peers_p || !bw.flags)
+      return SPBLAS_GFX950_STATUS_SUCCESS;
+    const int rc_w = launch_step_wait(h, bw.flags, bw.n_peers, bw.step, bw.timeout_ms, bw.status_dev);
+    bw.flags = nullptr;
+    return rc_w;
+  };
   if (pl->vfree) {
     // one workgroup per bin: the bin's window of the caller's values in LDS, vf_waves wavefronts on the bin's stream
     const int32_t* binblk = static_cast<const int32_t*>(pl->s_binblk);
@@ -3582,6 +3593,9 @@ static int sliced_reduce_typed(spblas_gfx950_handle_t h, spblas_gfx950_plan_s* p
     int64_t grid = env_int("SPBLAS_GFX950_PB_VF_GRID", h->num_cus > 0 ? h->num_cus : 256);
     if (grid < 1 || grid > wb_end - wb_begin)
       grid = wb_end - wb_begin;
+    const int rc_w = wait_hook();  // (this kernel stores into the peers' copies itself: K = 1, no combine)
+    if (rc_w)
+      return rc_w;
     SPB_HIP(hipLaunchKernel(pb_reduce_vf_fn<T>(pl->vf_waves, UBv, pl->enc8 != 0), dim3((unsigned) grid),
                             dim3(pl->vf_waves * 64), args, lds, s));
   } else {
@@ -3621,16 +3635,6 @@ static int sliced_reduce_typed(spblas_gfx950_handle_t h, spblas_gfx950_plan_s* p
                            static_cast<const T*>(pl->s_rpartial), static_cast<T*>(y), alpha, beta, pl->rows_per_blk,
                            binrow, pl->n_rblk, rowmap, piece_out);
     } else {
-      // fused multi-GPU step, throughput form: the wait for the PREVIOUS step's barrier goes right before the kernel that
-      // stores into the peers' copies of y -- everything before it overlaps the peers' stores still crossing the links
-      auto wait_hook = [&]() -> int {
-        auto& bw = h->bcast_wait;
-        if (!peers_p || !bw.flags)
-          return SPBLAS_GFX950_STATUS_SUCCESS;
-        const int rc_w = launch_step_wait(h, bw.flags, bw.n_peers, bw.step, bw.timeout_ms, bw.status_dev);
-        bw.flags = nullptr;
-        return rc_w;
-      };
       if (!(K > 1 && r_hi > r_lo)) {
         const int rc_w = wait_hook();
         if (rc_w)

@@ -451,6 +451,11 @@ class FusedShardedSpMV:
             self.value_free = bool(si_.get("value_free"))
             # buffers: two copies of y, one flag array (slot q = last step signalled by rank q)
             self.chunks = max(0, int(chunks))
+            if self.chunks and self.value_free:
+                # (spblas_gfx950_spmv_step_bcast_chunked refuses a plan that reads the caller's values on every call: said
+                # here, on every rank together, and not at the first step_dependent())
+                raise RuntimeError("FusedShardedSpMV: chunks > 0 (step_dependent) needs a plan that owns its values; a "
+                                   "value-free plan reads the caller's array on every call and has no chunked step")
             if self.world * max(self.chunks, 1) > 64:
                 raise RuntimeError("FusedShardedSpMV: ranks x chunks must not exceed 64")
             self._bufs = [_IpcBuffer(self.m * item), _IpcBuffer(self.m * item), _IpcBuffer(self.world * 8, uncached=True),

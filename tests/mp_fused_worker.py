@@ -81,8 +81,39 @@ def main():
         dist.all_gather_object(gathered, y.cpu().numpy().tobytes())
         assert all(gb == gathered[0] for gb in gathered), "value-free plans: ranks hold different y"
         a_loc.values().copy_(saved_vals)                 # (bit-exact restore: the rest of the worker compares bits)
-        op_vf.close()
         print("FUSED_VFREE_OK", flush=True)
+        # the throughput form on the value-free plan: the wait for step k-1 armed inside step k must reach the value-free
+        # reduce too (it stores into the peers' copies itself).  The sequence of the plan-sharing leg below, bit for bit
+        # against step() on the same plan: a late or lost peer store, or a buffer overwritten too early, shows
+        refs_vf = {}
+        for sc in (1.0, -2.0, 0.25, 4.0):
+            refs_vf[sc] = op_vf.step(x * sc).clone()
+            torch.cuda.synchronize()
+            op_vf.check_status()
+        err = np.abs(refs_vf[0.25].cpu().numpy().astype(np.float64) - 0.25 * ref.astype(np.float64))
+        assert (err <= tol * 0.25 * absrow + 1e-30).all(), f"rank {rank} value-free step with x / 4: parity failed"
+        for sc in (1.0, -2.0, 0.25):
+            op_vf.step_pipelined(x * sc)
+        y_last = op_vf.flush()
+        torch.cuda.synchronize()
+        op_vf.check_status()
+        assert torch.equal(y_last, refs_vf[0.25]), "value-free plan, pipelined steps: last y differs"
+        assert torch.equal(op_vf.step(x * 4.0), refs_vf[4.0]), "value-free plan: dependent step after pipelined ones differs"
+        torch.cuda.synchronize()
+        op_vf.check_status()
+        op_vf.step_pipelined(x * -2.0)
+        assert torch.equal(op_vf.step(x), refs_vf[1.0]), "value-free plan: step() must flush a pending pipelined step first"
+        torch.cuda.synchronize()
+        op_vf.check_status()
+        op_vf.close()
+        # step_dependent() has no value-free form: said by the constructor, on every rank, with the reason
+        try:
+            sharded.FusedShardedSpMV(a_loc, bounds, info=info_vf, timeout_ms=15000, chunks=2, shared_device=True)
+        except RuntimeError as e:
+            assert "value-free" in str(e) and "chunks" in str(e), str(e)
+        else:
+            raise AssertionError("FusedShardedSpMV accepted chunks > 0 on a value-free plan")
+        print("FUSED_VFREE_PIPELINED_OK", flush=True)
     # the selection helper bench.py uses: adopted only when bit-identical to a reference path on every rank
     plans = []
     for q in range(world):

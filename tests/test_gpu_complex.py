@@ -11,13 +11,13 @@ import torch
 
 import spblas_reference_amd as sp
 import util
+from ladder import check_complex
 from spblas_reference_amd import _capi
 from spblas_reference_amd.api import _Handle
 
 pytestmark = pytest.mark.gpu
 
 CDT = {np.complex64: torch.complex64, np.complex128: torch.complex128}
-EPS = {np.complex64: float(np.finfo(np.float32).eps), np.complex128: float(np.finfo(np.float64).eps)}
 CONJ = [(False, False), (True, False), (False, True), (True, True)]
 
 
@@ -69,17 +69,7 @@ def view(values, rowptr, colind, shape, nnz, dev, offset64=False):
     return sp.csr_view(to_dev(values, dev), to_dev(rp, dev), to_dev(colind, dev), shape, nnz)
 
 
-def check(y, y_ref, absrow, dtype, row_len, what=""):
-    """Norm-wise bound per element (util.assert_parity's form, on the complex modulus): the error of a k-entry complex dot
-    product in the value type is at most ~(k + 2) * 2 eps * sum |a||x|."""
-    eps = EPS[dtype]
-    k = np.maximum(np.asarray(row_len, dtype=np.float64), 16.0)
-    if y_ref.ndim == 2 and k.ndim == 1:
-        k = k[:, None]
-    err = np.abs(y.astype(np.complex128) - y_ref)
-    bound = 4.0 * k * eps * absrow + 1e-30
-    bad = ~(err <= bound)
-    assert not bad.any(), f"{what}: {bad.sum()} entries off; worst ratio {(err / bound).max():.3g}"
+check = check_complex   # (the bound lives in tests/ladder.py, shared with the ladder tests)
 
 
 def row_lengths(rowptr):

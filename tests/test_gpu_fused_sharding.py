@@ -29,13 +29,16 @@ def _bench_full(line):
 def test_fused_sharded_spmv_multiprocess(gpu, world, dt, stripes):
     """stripes > 1: the reduces of contiguous bin groups alternate between two streams (the groups need not
     divide the bins evenly).  FUSED_VFREE: the same exchange on a value-free local plan (round 6), values rewritten in place
-    between steps."""
+    between steps; then the throughput form (step_pipelined x 3, flush, a dependent step, step_pipelined + step) on that
+    plan, compared bit for bit with step(), and the constructor's refusal of chunks > 0."""
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", MASTER_ADDR="127.0.0.1", FUSED_STRIPES=str(stripes), FUSED_VFREE="1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={world}",
            "--master-addr", "127.0.0.1", "--master-port", str(29650 + world + (7 if dt == "f64" else 0)),
            os.path.join(ROOT, "tests", "mp_fused_worker.py"), dt]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
     assert r.returncode == 0 and "FUSED_OK" in r.stdout and "FUSED_VFREE_OK" in r.stdout, (r.stdout[-3000:], r.stderr[-3000:])
+    # ... and step_pipelined / flush / step on the value-free plan, bit for bit with step(); chunks > 0 refused by the constructor
+    assert "FUSED_VFREE_PIPELINED_OK" in r.stdout, (r.stdout[-3000:], r.stderr[-3000:])
 
 
 # (at most four ranks, so that at most six processes hold the one GPU at a time: the ranks, the torch.distributed.run

@@ -14,6 +14,7 @@ import scipy.sparse as sps
 import torch
 
 import fullcheck as F
+from ladder import bits_equal, check_lowp
 import spblas_reference_amd as sp
 from spblas_reference_amd import _capi, generate
 from spblas_reference_amd.api import _Handle
@@ -22,8 +23,6 @@ pytestmark = pytest.mark.gpu
 
 LOWP = [torch.float16, torch.bfloat16]
 VT = {torch.float16: _capi.F16, torch.bfloat16: _capi.BF16}
-MANT = {torch.float16: 10, torch.bfloat16: 7}   # stored mantissa bits
-EMIN = {torch.float16: -14, torch.bfloat16: -126}
 
 
 def _name(dt):
@@ -62,39 +61,7 @@ def host_mat(host, shape, absolute=False):
     return sps.csr_matrix((np.abs(v) if absolute else v, colind, rowptr), shape=shape)
 
 
-def half_ulp(v, dt):
-    e = torch.floor(torch.log2(v.clamp(min=1e-300))).clamp(min=EMIN[dt])
-    return 0.5 * torch.exp2(e - MANT[dt])
-
-
-def check(y, ref, absrow, row_len, dt, what=""):
-    """y: 16-bit device tensor; ref / absrow: float64 (numpy or torch) of y's shape; row_len: entries per row."""
-    yd = y.double()
-    ref = torch.as_tensor(ref, dtype=torch.float64).to(yd.device)
-    absrow = torch.as_tensor(absrow, dtype=torch.float64).to(yd.device)
-    k = torch.as_tensor(np.asarray(row_len, dtype=np.float64)).to(yd.device)
-    if ref.dim() == 2 and k.dim() == 1:
-        k = k[:, None]
-    nan = torch.isnan(ref)
-    assert torch.equal(torch.isnan(yd), nan), f"{what}: NaN positions differ"
-    inf = torch.isinf(ref)
-    assert torch.equal(yd[inf], ref[inf]), f"{what}: inf entries differ"
-    acc = (k + 2.0) * 2.0 ** -24 * absrow
-    bound = half_ulp(ref.abs() + acc, dt) + acc
-    bad = ~nan & ~inf & ~((yd - ref).abs() <= bound)
-    if bool(bad.any()):
-        idx = bad.nonzero()[:5].tolist()
-        raise AssertionError(f"{what}: {int(bad.sum())} elements out of bound, first at {idx}: "
-                             f"{[(yd[tuple(i)].item(), ref[tuple(i)].item(), bound[tuple(i)].item()) for i in idx]}")
-
-
-def bits_equal(y, ref64, dt):
-    """y (16-bit) equals ref64 rounded to dt bit for bit (+0 / -0 taken as one value)."""
-    r = torch.as_tensor(ref64, dtype=torch.float64).to(y.device).to(dt)
-    yb, rb = y.view(torch.int16), r.view(torch.int16)
-    yb = torch.where(y == 0, torch.zeros_like(yb), yb)
-    rb = torch.where(r == 0, torch.zeros_like(rb), rb)
-    return torch.equal(yb, rb)
+check = check_lowp   # (the bound lives in tests/ladder.py, shared with the ladder tests)
 
 
 def ptr(t):
