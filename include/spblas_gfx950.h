@@ -418,7 +418,11 @@ int spblas_gfx950_spgemm_numeric(spblas_gfx950_handle_t handle, spblas_gfx950_sp
 /* Introspection of a state after spgemm_symbolic (no reference counterpart; the tests and bench.py use it):
  * info[0] = nnz(C), info[1] = rows with 65..256 products (the wave-per-row bin), info[2] = those of them that are
  * "direct" -- product count == structural length and an A row of one round of loads: sorted in registers by the
- * persistent kernel, no hash --, info[3] = 1 when later fills accumulate by recorded rank, info[4..7] = 0. */
+ * persistent kernel, no hash --, info[3] = 1 when later fills accumulate by recorded rank, info[4] = lanes that walk
+ * one row of B together (4, 8 or 16, from B's mean row length; 0 before a symbolic pass), info[5] = rows with 1..64
+ * products, info[6] = rows with 257..1024, info[7] = rows with more than 4096 (the dense accumulator).  The product
+ * counts include the addend's row; a row the persistent kernel takes counts under info[1] whatever its count.  Rows
+ * with 1025..4096 products are the rows of C minus info[1], info[5..7] and the rows without a product. */
 int spblas_gfx950_spgemm_info(spblas_gfx950_spgemm_t state, int64_t info[8]);
 
 /* Four-argument SpGEMM  C = alpha*A*B + beta*D  (the reference

@@ -456,7 +456,8 @@ class spgemm_state_t:
             return {}
         raw = (ctypes.c_int64 * 8)()
         check(_capi.lib().spblas_gfx950_spgemm_info(self._state, raw), "spblas_gfx950_spgemm_info")
-        return {"nnz_c": raw[0], "wave_per_row_rows": raw[1], "direct_rows": raw[2], "fills_by_rank": bool(raw[3])}
+        return {"nnz_c": raw[0], "wave_per_row_rows": raw[1], "direct_rows": raw[2], "fills_by_rank": bool(raw[3]),
+                "lanes_per_b_row": raw[4], "bin1_rows": raw[5], "bin3_rows": raw[6], "dense_rows": raw[7]}
 
     def __del__(self):
         try:

@@ -1865,6 +1865,8 @@ static void spgemm_release(spblas_gfx950_spgemm_s* st, hipStream_t s) {
   st->dense_vals = nullptr;
   st->dense_vals_type = -1;
   st->c_nnz = -1;
+  for (int b = 0; b <= SPG_NBINS; ++b)  // (a result without rows keeps no counts of the one before it)
+    st->bin_off[b] = 0;
 }
 
 } // namespace spb
@@ -1901,6 +1903,10 @@ int spblas_gfx950_spgemm_info(spblas_gfx950_spgemm_t st, int64_t info[8]) {
   info[1] = st->bin_off[3] - st->bin_off[2];
   info[2] = st->dir_desc ? st->n_dir : 0;
   info[3] = st->r_ready ? 1 : 0;
+  info[4] = st->c_nnz >= 0 ? st->sub : 0;
+  info[5] = st->bin_off[2] - st->bin_off[1];
+  info[6] = st->bin_off[4] - st->bin_off[3];
+  info[7] = st->bin_off[6] - st->bin_off[5];
   return SPBLAS_GFX950_STATUS_SUCCESS;
 }
 

@@ -10,6 +10,7 @@ import pytest
 import torch
 
 import gpu_util as G
+import ladder
 import spblas_reference_amd as sp
 import util
 from oracle import oracle
@@ -413,7 +414,8 @@ def test_spgemm_direct_rows(gpu, dtype, b_len, n):
     products = np.add.reduceat(np.diff(b_h[1])[ac], ar[:-1])[np.diff(ar) > 0] if len(ac) else np.zeros(0)
     wave_rows = int(((products > 64) & (products <= 256)).sum())
     assert info["nnz_c"] == got[0] and info["wave_per_row_rows"] == wave_rows
-    assert 0.5 * wave_rows <= info["direct_rows"] <= wave_rows and wave_rows > 100
+    sortable = int(ladder.is_sortable(ar, ac, b_h[1]).sum())       # the classification rule, restated on the host
+    assert info["direct_rows"] == sortable and 0.5 * wave_rows <= sortable <= wave_rows and wave_rows > 100
     if n < 10000:
         assert got[0] < 0.9 * products[products > 0].sum()  # (shared columns everywhere: C is much smaller than the product list)
     nnz = state.result_nnz()
