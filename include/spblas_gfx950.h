@@ -74,8 +74,8 @@ typedef enum spblas_gfx950_datatype {
   /* complex, interleaved (re, im) like std::complex<float / double>; alpha / beta point at ONE complex host scalar.
    * SpMV (op N) and SpMM on CSR with int32 columns only: spmv_plan_create (AUTO / VECTOR / ROWBLOCK; SLICED returns
    * STATUS_NOT_SUPPORTED), spblas_gfx950_spmv[_conj], spblas_gfx950_spmm[_strided[_conj]].  The other entry points that take a
-   * value type (spgemm_numeric[_addend], csr_add_numeric, csr_transpose, scale, sptrsv_solve) return STATUS_NOT_SUPPORTED
-   * for them, before any other check; so do plan_update_values / plan_detach and the two-stage / multi-GPU calls on a
+   * value type (spgemm_numeric[_addend], csr_add_numeric, csr_transpose, scale, sptrsv_solve, sptrsm_solve) return
+   * STATUS_NOT_SUPPORTED for them, before any other check; so do plan_update_values / plan_detach and the two-stage / multi-GPU calls on a
    * complex plan. */
   SPBLAS_GFX950_C32 = 2, /* std::complex<float>  */
   SPBLAS_GFX950_C64 = 3, /* std::complex<double> */
@@ -84,8 +84,8 @@ typedef enum spblas_gfx950_datatype {
    * and SpMM on CSR with int32 columns only: spmv_plan_create (AUTO / VECTOR / ROWBLOCK; AUTO never picks SLICED, SLICED
    * returns STATUS_NOT_SUPPORTED), spblas_gfx950_spmv, spblas_gfx950_spmm[_strided], spmm_inspect.  op = T, the _conj entry
    * points and every other entry point that takes a value type (spgemm_numeric[_addend], csr_add_numeric, csr_transpose,
-   * scale, sptrsv_solve) return STATUS_NOT_SUPPORTED for them, before any other check; so do plan_update_values /
-   * plan_detach / spmv_expand / spmv_reduce_rows on a 16-bit plan. */
+   * scale, sptrsv_solve, sptrsm_solve) return STATUS_NOT_SUPPORTED for them, before any other check; so do
+   * plan_update_values / plan_detach / spmv_expand / spmv_reduce_rows on a 16-bit plan. */
   SPBLAS_GFX950_F16 = 4, /* IEEE binary16 (torch.float16) */
   SPBLAS_GFX950_BF16 = 5 /* bfloat16 (torch.bfloat16)     */
 } spblas_gfx950_datatype;
@@ -117,7 +117,7 @@ int spblas_gfx950_last_hip_error(void);
 /* stream: a hipStream_t (NULL = the null stream), cf. hip_allocator(hipStream_t),
  * vendor/rocsparse/hip_allocator.hpp:22.
  * Graph capture: the execute calls that take a plan or a state whose structure is known (spblas_gfx950_spmv,
- * spblas_gfx950_spmm, spblas_gfx950_sptrsv_solve, spblas_gfx950_spgemm_numeric after the first fill) only launch kernels
+ * spblas_gfx950_spmm, spblas_gfx950_sptrsv_solve / _sptrsm_solve, spblas_gfx950_spgemm_numeric after the first fill) only launch kernels
  * and memsets on this stream and may be recorded with hipStreamBeginCapture and replayed.  Nothing is allocated on a
  * capturing stream: a call that would have to (plan creation, inspect, symbolic passes, the first execute of a plan that
  * sizes a workspace) returns SPBLAS_GFX950_STATUS_NOT_SUPPORTED there -- run it once outside the capture.
@@ -496,6 +496,33 @@ int spblas_gfx950_sptrsv_status(spblas_gfx950_handle_t handle, spblas_gfx950_trs
 int spblas_gfx950_sptrsv_solve(spblas_gfx950_handle_t handle, spblas_gfx950_trsv_t plan, int64_t m, int64_t nnz,
                                const void* alpha, const int32_t* rowptr, const int32_t* colind, const void* values,
                                const void* b, void* x, int value_type);
+/* The same solve for n right-hand sides in one call:  X(:, j) = inv(alpha*A) B(:, j),  j = 0 .. n-1  (no reference
+ * counterpart: the reference solves one vector).  The triangle read is the one sptrsv_solve reads; `plan` is a plan of
+ * sptrsv_create, unchanged -- one plan serves both calls, in any order.  Every level of the plan is handed over once for
+ * all n columns.
+ *   value types   F32 / F64; C32 / C64 / F16 / BF16 return STATUS_NOT_SUPPORTED before any other check.  The checks that
+ *                 follow are those of sptrsv_solve, in its order: handle, pointers, plan against m / nnz.
+ *   layouts       element (i, j) of B lives at B[i*b_row_stride + j*b_col_stride], likewise X.  Each operand is
+ *                 layout_right (column stride 1, row stride >= n) or layout_left (row stride 1, column stride >= m): the
+ *                 rule of spblas_gfx950_spmm_strided; B and X may differ.  Anything else, or n < 0: STATUS_INVALID_SIZE.
+ *                 n == 0: success, nothing is launched, X is not touched.  An X that is layout_right with rows a multiple of
+ *                 16 bytes apart is read and written in 16-byte pieces (any base alignment: the columns before the first
+ *                 and after the last aligned piece go one by one); every other X element by element through its strides.
+ *   n == 1        with B and X contiguous vectors of m elements the call IS sptrsv_solve: the same kernels, the same bits.
+ *   aliasing      B == X with equal strides is allowed (in place).  Any other overlap of B and X is a caller error and is
+ *                 not checked.
+ *   results       the same plan, device and arguments give the same bits; the bits of a column do not depend on the values
+ *                 of the other columns (they do depend on n, the layouts and the alignment of X, which choose how many
+ *                 lanes share a row's entries).
+ *   capture       recordable on the terms of sptrsv_solve: the first solve of a plan, by either call, sizes the plan's
+ *                 control words and returns STATUS_NOT_SUPPORTED on a capturing stream; later solves only launch kernels.
+ *   status        always one launch per wide level and one per run of narrow levels -- there is no cooperative form, so no
+ *                 device-side wait that could give up: sptrsv_status reports 0 after it, and a give-up of an earlier
+ *                 sptrsv_solve on the plan is reported by this call as by the next sptrsv_solve. */
+int spblas_gfx950_sptrsm_solve(spblas_gfx950_handle_t handle, spblas_gfx950_trsv_t plan, int64_t m, int64_t nnz,
+                               int64_t n, const void* alpha, const int32_t* rowptr, const int32_t* colind,
+                               const void* values, const void* B, int64_t b_row_stride, int64_t b_col_stride,
+                               void* X, int64_t x_row_stride, int64_t x_col_stride, int value_type);
 
 /* ---- scale:  values[i] *= alpha  (algorithms/scale_impl.hpp:13-19) --------------------------- */
 /* In-place scaling of a matrix's value array or of a dense vector (n elements, device memory).  A SLICED

@@ -853,4 +853,67 @@ void triangular_solve(A&& a, Triangle t, DiagonalStorage d, B&& b, X&& x) {
   triangular_solve(info, a, t, d, b, x);
 }
 
+// ---- a block of right-hand sides: X(:, j) = inv(A) B(:, j) for every column in one solve (spblas_gfx950_sptrsm_solve).
+// B (possibly scaled) and X are mdspan_row_major; the state is the vector solve's, so one info serves both forms. ----------
+namespace __gfx950 {
+template <typename A, typename Triangle, typename DiagonalStorage, typename B, typename X>
+void trsm_prepare(trsv_state_t& st, A&& a, Triangle, DiagonalStorage, B&& b, X&& x) {
+  static_assert(std::is_same_v<Triangle, upper_triangle_t> || std::is_same_v<Triangle, lower_triangle_t>);
+  static_assert(std::is_same_v<DiagonalStorage, implicit_unit_diagonal_t> ||
+                std::is_same_v<DiagonalStorage, explicit_diagonal_t>);
+  auto ab = __detail::get_ultimate_base(a);
+  auto bb = __detail::get_ultimate_base(b);
+  static_assert(std::is_same_v<typename decltype(ab)::scalar_type, std::remove_cv_t<typename decltype(bb)::value_type>> &&
+                    std::is_same_v<typename decltype(ab)::scalar_type, typename std::remove_cvref_t<X>::value_type>,
+                "triangular_solve: B and X must have A's value type");
+  reject_conjugated(__detail::is_conjugated(a) || __detail::is_conjugated(b));
+  if (ab.shape()[0] != ab.shape()[1] || static_cast<std::int64_t>(x.extent(0)) != static_cast<std::int64_t>(ab.shape()[1]) ||
+      static_cast<std::int64_t>(bb.extent(0)) != static_cast<std::int64_t>(ab.shape()[0]) || bb.extent(1) != x.extent(1)) {
+    throw std::invalid_argument("triangular_solve: matrix and vector dimensions are incompatible.");
+  }
+  const int uplo = std::is_same_v<Triangle, upper_triangle_t> ? SPBLAS_GFX950_UPPER : SPBLAS_GFX950_LOWER;
+  const int diag =
+      std::is_same_v<DiagonalStorage, implicit_unit_diagonal_t> ? SPBLAS_GFX950_DIAG_UNIT : SPBLAS_GFX950_DIAG_EXPLICIT;
+  if (!st.matches(ab.rowptr().data(), ab.colind().data(), ab.shape()[0], ab.size(), uplo, diag)) {
+    st.inspect(ab.shape()[0], ab.size(), ab.rowptr().data(), ab.colind().data(), uplo, diag);
+  }
+}
+} // namespace __gfx950
+
+template <typename A, typename Triangle, typename DiagonalStorage, typename B, typename X>
+  requires(__detail::has_csr_base<A> && __detail::has_dense_base<B> && __detail::is_dense<std::remove_cvref_t<X>>::value)
+void triangular_solve_inspect(operation_info_t& info, A&& a, Triangle t, DiagonalStorage d, B&& b, X&& x) {
+  __gfx950::trsm_prepare(__gfx950::trsv_state_of(info), a, t, d, b, x);
+}
+template <typename A, typename Triangle, typename DiagonalStorage, typename B, typename X>
+  requires(__detail::has_csr_base<A> && __detail::has_dense_base<B> && __detail::is_dense<std::remove_cvref_t<X>>::value)
+operation_info_t triangular_solve_inspect(A&& a, Triangle t, DiagonalStorage d, B&& b, X&& x) {
+  operation_info_t info;
+  triangular_solve_inspect(info, a, t, d, b, x);
+  return info;
+}
+template <typename A, typename Triangle, typename DiagonalStorage, typename B, typename X>
+  requires(__detail::has_csr_base<A> && __detail::has_dense_base<B> && __detail::is_dense<std::remove_cvref_t<X>>::value)
+void triangular_solve(operation_info_t& info, A&& a, Triangle t, DiagonalStorage d, B&& b, X&& x) {
+  auto& st = __gfx950::trsv_state_of(info);
+  __gfx950::trsm_prepare(st, a, t, d, b, x);
+  auto ab = __detail::get_ultimate_base(a);
+  auto bb = __detail::get_ultimate_base(b);
+  using T = typename decltype(ab)::scalar_type;
+  const T alpha = static_cast<T>(__detail::get_scaling_factor(a).value_or(1.0));
+  const auto beta = __detail::get_scaling_factor(b);
+  st.template solve_matrix<T>(alpha, ab.rowptr().data(), ab.colind().data(), ab.values().data(), x.extent(1),
+                              bb.data_handle(), bb.stride(0), bb.stride(1), x.data_handle(), x.stride(0), x.stride(1));
+  if (beta.has_value()) {  // the solve is linear in B: the factor is applied to X afterwards
+    __gfx950::handle_t h;
+    __gfx950::scale_dense<T>(h, static_cast<T>(*beta), x.data_handle(), x.extent(0), x.extent(1), x.stride(0), x.stride(1));
+  }
+}
+template <typename A, typename Triangle, typename DiagonalStorage, typename B, typename X>
+  requires(__detail::has_csr_base<A> && __detail::has_dense_base<B> && __detail::is_dense<std::remove_cvref_t<X>>::value)
+void triangular_solve(A&& a, Triangle t, DiagonalStorage d, B&& b, X&& x) {
+  operation_info_t info;
+  triangular_solve(info, a, t, d, b, x);
+}
+
 } // namespace spblas

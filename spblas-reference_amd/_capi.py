@@ -116,6 +116,9 @@ PROTOTYPES = [
     ("spblas_gfx950_sptrsv_status", c_int, [c_void_p, c_void_p, ctypes.POINTER(c_int)]),
     ("spblas_gfx950_sptrsv_solve", c_int,
      [c_void_p, c_void_p, c_i64, c_i64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int]),
+    ("spblas_gfx950_sptrsm_solve", c_int,
+     [c_void_p, c_void_p, c_i64, c_i64, c_i64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_i64, c_void_p,
+      c_i64, c_i64, c_int]),
     ("spblas_gfx950_spgemm_set_addend", c_int, [c_void_p, c_void_p, c_i64, c_void_p, c_void_p]),
     ("spblas_gfx950_spgemm_numeric_addend", c_int,
      [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,

@@ -1529,13 +1529,16 @@ def _trsv_operands(a, uplo, diag, b, x):
         raise NotImplementedError("gfx950 triangular_solve: x must be a plain vector")
     b = get_ultimate_base(b)  # scaled(alpha, b) is allowed (examples/simple_sptrsv.cpp:49-53): applied to x afterwards
     m, n = a_base.shape()
-    # the reference asserts squareness and matching vector lengths (triangular_solve_impl.hpp:50-53)
-    if m != n or not _is_tensor(b) or not _is_tensor(x) or b.dim() != 1 or x.dim() != 1 or x.numel() != n or \
-            b.numel() != m:
+    # the reference asserts squareness and matching vector lengths (triangular_solve_impl.hpp:50-53); two matrices of m rows and
+    # the same number of columns are a block of right-hand sides (spblas_gfx950_sptrsm_solve)
+    if m != n or not _is_tensor(b) or not _is_tensor(x) or b.dim() != x.dim() or b.dim() not in (1, 2) or \
+            x.shape[0] != n or b.shape[0] != m or (b.dim() == 2 and b.shape[1] != x.shape[1]):
         raise ValueError("triangular_solve: matrix and vector dimensions are incompatible.")
     if b.dtype != a_base.values().dtype or x.dtype != a_base.values().dtype:
         raise TypeError("triangular_solve: b and x must have A's value type")
-    if not (b.is_contiguous() and x.is_contiguous()):
+    if b.dim() == 2:
+        _dense_strides(b, m, b.shape[1]), _dense_strides(x, m, x.shape[1])  # row- or column-major, else ValueError
+    elif not (b.is_contiguous() and x.is_contiguous()):
         raise ValueError("triangular_solve: vectors must be contiguous")
     return a_base
 
@@ -1575,7 +1578,9 @@ def triangular_solve_inspect(*args):
 
 def triangular_solve(*args):
     """triangular_solve(a, uplo, diag, b, x) / triangular_solve(info, a, uplo, diag, b, x):
-    x = inv(A) b using only the named triangle of A (triangular_solve_impl.hpp:41-107)."""
+    x = inv(A) b using only the named triangle of A (triangular_solve_impl.hpp:41-107).  b and x may both be (m, n) tensors,
+    row- or column-major (windows of wider tensors included): X(:, j) = inv(A) B(:, j) for all columns in one solve.  A plan
+    made by triangular_solve_inspect with vectors serves matrices and the other way round."""
     if len(args) == 6:
         info, a, uplo, diag, b, x = args
     elif len(args) == 5:
@@ -1594,9 +1599,26 @@ def triangular_solve(*args):
     sa = get_scaling_factor(a)
     alpha = ct(1 if sa is None else sa)
     sb = get_scaling_factor(b)
+    bb = get_ultimate_base(b)
+    if x.dim() == 2:  # a block of right-hand sides: one solve, every level handed over once for all columns
+        m, n = x.shape
+        (brs, bcs), (xrs, xcs) = _dense_strides(bb, m, n), _dense_strides(x, m, n)
+        check(_capi.lib().spblas_gfx950_sptrsm_solve(hd.h, plan.plan, a_base.shape()[0], a_base.size(), n, ctypes.byref(alpha),
+                                                     _ptr(a_base.rowptr()), _ptr(a_base.colind()), _ptr(a_base.values()),
+                                                     _ptr(bb), brs, bcs, _ptr(x), xrs, xcs, vt), "triangular_solve")
+        if sb is not None and x.numel() > 0:
+            beta = ct(sb)
+            if x.is_contiguous() or x.t().is_contiguous():
+                check(_capi.lib().spblas_gfx950_scale(hd.h, x.numel(), ctypes.byref(beta), _ptr(x), vt), "triangular_solve")
+            else:  # a window of a wider tensor: its lines one by one (the elements between them are not X's)
+                lines = x if xcs == 1 else x.t()
+                for i in range(lines.shape[0]):
+                    check(_capi.lib().spblas_gfx950_scale(hd.h, lines.shape[1], ctypes.byref(beta), _ptr(lines[i]), vt),
+                          "triangular_solve")
+        return
     check(_capi.lib().spblas_gfx950_sptrsv_solve(hd.h, plan.plan, a_base.shape()[0], a_base.size(),
                                                  ctypes.byref(alpha), _ptr(a_base.rowptr()), _ptr(a_base.colind()),
-                                                 _ptr(a_base.values()), _ptr(get_ultimate_base(b)), _ptr(x), vt),
+                                                 _ptr(a_base.values()), _ptr(bb), _ptr(x), vt),
           "triangular_solve")
     if sb is not None:  # the solve is linear in b: x = inv(A) (s b) = s inv(A) b
         beta = ct(sb)

@@ -21,6 +21,7 @@ void preload_spmm();
 void preload_spgemm();
 void preload_transpose();
 void preload_sptrsv();
+void preload_sptrsm();
 void preload_multigpu();
 } // namespace spb
 
@@ -82,6 +83,7 @@ int spblas_gfx950_create(spblas_gfx950_handle_t* handle, void* stream) {
       spb::preload_spgemm();
       spb::preload_transpose();
       spb::preload_sptrsv();
+      spb::preload_sptrsm();
       spb::preload_multigpu();
     });
   return SPBLAS_GFX950_STATUS_SUCCESS;

@@ -31,6 +31,7 @@
 #include "complex_api.hpp"
 #include "lowp_api.hpp"
 #include "scan.hpp"
+#include "trsv_plan.hpp"
 
 #include <algorithm>
 #include <cstdlib>
@@ -45,32 +46,7 @@ static int env_int(const char* name, int def) {  // tuning / test hook
 #define TRSV_NARROW 2048       // inspect: frontiers with fewer rows are advanced by the single-workgroup kernel
 #define TRSV_BLOCK_THREADS 1024
 
-struct spblas_gfx950_trsv_s {
-  int64_t m = 0, nnz = 0;
-  int uplo = 0, diag = 0;
-  int32_t* order = nullptr;      // [m] rows sorted by level
-  int32_t* level_ptr = nullptr;  // [n_levels + 1] device copy
-  std::vector<int32_t> h_level_ptr;
-  // launch groups: {first_level, last_level (exclusive), wide ? 1 : 0}
-  struct group_t {
-    int32_t l0, l1, wide;
-  };
-  std::vector<group_t> groups;
-  int64_t max_width = 0;
-  int lanes = 8;  // lanes per row in the solve kernels
-  int narrow = 128;      // levels with fewer rows are "narrow": walked by one workgroup
-  bool coop_ok = false;  // the solve is ONE cooperative launch (trsv_coop_kernel)
-  int32_t* tickets = nullptr;         // device: status word and the grid barrier's counters / release lines
-  // pinned, device-visible host word: a solve whose grid barrier ran into its poll bound sets it (system-scope store, only
-  // on that path), the NEXT solve on this plan -- and spblas_gfx950_sptrsv_status -- reads it without touching the stream
-  int* sticky = nullptr;
-};
-
 namespace spb {
-
-__device__ __forceinline__ bool trsv_strict(int c, int r, int upper) {
-  return upper ? c > r : c < r;
-}
 
 // in-degree of every row (strict entries) and out-degree of every column (how many rows read x_k)
 __global__ __launch_bounds__(256) void trsv_degree_kernel(int64_t m, const int32_t* __restrict__ rowptr,
@@ -636,12 +612,8 @@ __global__ __launch_bounds__(TRSV_BLOCK_THREADS) void trsv_chain_kernel(int l0, 
   }
 }
 
-template <typename T, int G>
-static int trsv_solve_typed(spblas_gfx950_handle_t h, spblas_gfx950_trsv_s* pl, const int32_t* rowptr,
-                            const int32_t* colind, const T* values, T alpha, const T* b, T* x) {
+int trsv_begin_solve(spblas_gfx950_handle_t h, spblas_gfx950_trsv_s* pl, bool* capturing_out, size_t* bar_off_out) {
   hipStream_t s = h->stream;
-  const int upper = pl->uplo == SPBLAS_GFX950_UPPER, unit = pl->diag == SPBLAS_GFX950_DIAG_UNIT;
-  const int m = (int) pl->m;
   const size_t ng = pl->groups.size();
   const int cus = h->num_cus > 0 ? h->num_cus : 256;
   // [ng + 1] = status word (the leading words are unused since the self-scheduling form left), then (32-int aligned) the
@@ -651,6 +623,8 @@ static int trsv_solve_typed(spblas_gfx950_handle_t h, spblas_gfx950_trsv_s* pl, 
   // recorded with: no cooperative launch (the kernel node does not carry the co-residency guarantee of the launch: replays
   // were seen to leave rows unsolved), no allocation (the first solve of a plan must run outside the capture).
   const bool capturing = stream_capturing(s);
+  *capturing_out = capturing;
+  *bar_off_out = bar_off;
   if (capturing && !pl->tickets)
     return SPBLAS_GFX950_STATUS_NOT_SUPPORTED;
   if (!pl->tickets) {
@@ -674,6 +648,21 @@ static int trsv_solve_typed(spblas_gfx950_handle_t h, spblas_gfx950_trsv_s* pl, 
     }
   }
   SPB_HIP(hipMemsetAsync(pl->tickets, 0, ctl_ints * 4, s));
+  return SPBLAS_GFX950_STATUS_SUCCESS;
+}
+
+template <typename T, int G>
+static int trsv_solve_typed(spblas_gfx950_handle_t h, spblas_gfx950_trsv_s* pl, const int32_t* rowptr,
+                            const int32_t* colind, const T* values, T alpha, const T* b, T* x) {
+  hipStream_t s = h->stream;
+  const int upper = pl->uplo == SPBLAS_GFX950_UPPER, unit = pl->diag == SPBLAS_GFX950_DIAG_UNIT;
+  const int m = (int) pl->m;
+  const size_t ng = pl->groups.size();
+  const int cus = h->num_cus > 0 ? h->num_cus : 256;
+  bool capturing = false;
+  size_t bar_off = 0;
+  if (const int rc = trsv_begin_solve(h, pl, &capturing, &bar_off))
+    return rc;
   int* status = pl->tickets + ng + 1;
   int* sticky = pl->sticky;
   const int spin_limit = env_int("SPBLAS_GFX950_TRSV_SPIN_LIMIT", 1 << 22);  // ~ seconds of polling
