@@ -54,6 +54,7 @@ typedef struct spblas_gfx950_handle_s* spblas_gfx950_handle_t;
 typedef struct spblas_gfx950_plan_s* spblas_gfx950_plan_t;
 typedef struct spblas_gfx950_spgemm_s* spblas_gfx950_spgemm_t;
 typedef struct spblas_gfx950_trsv_s* spblas_gfx950_trsv_t;
+typedef struct spblas_gfx950_ilu0_s* spblas_gfx950_ilu0_t;
 
 typedef enum spblas_gfx950_status {
   SPBLAS_GFX950_STATUS_SUCCESS = 0,
@@ -74,7 +75,7 @@ typedef enum spblas_gfx950_datatype {
   /* complex, interleaved (re, im) like std::complex<float / double>; alpha / beta point at ONE complex host scalar.
    * SpMV (op N) and SpMM on CSR with int32 columns only: spmv_plan_create (AUTO / VECTOR / ROWBLOCK; SLICED returns
    * STATUS_NOT_SUPPORTED), spblas_gfx950_spmv[_conj], spblas_gfx950_spmm[_strided[_conj]].  The other entry points that take a
-   * value type (spgemm_numeric[_addend], csr_add_numeric, csr_transpose, scale, sptrsv_solve, sptrsm_solve) return
+   * value type (spgemm_numeric[_addend], csr_add_numeric, csr_transpose, scale, sptrsv_solve, sptrsm_solve, ilu0_factor) return
    * STATUS_NOT_SUPPORTED for them, before any other check; so do plan_update_values / plan_detach and the two-stage / multi-GPU calls on a
    * complex plan. */
   SPBLAS_GFX950_C32 = 2, /* std::complex<float>  */
@@ -84,7 +85,7 @@ typedef enum spblas_gfx950_datatype {
    * and SpMM on CSR with int32 columns only: spmv_plan_create (AUTO / VECTOR / ROWBLOCK; AUTO never picks SLICED, SLICED
    * returns STATUS_NOT_SUPPORTED), spblas_gfx950_spmv, spblas_gfx950_spmm[_strided], spmm_inspect.  op = T, the _conj entry
    * points and every other entry point that takes a value type (spgemm_numeric[_addend], csr_add_numeric, csr_transpose,
-   * scale, sptrsv_solve, sptrsm_solve) return STATUS_NOT_SUPPORTED for them, before any other check; so do
+   * scale, sptrsv_solve, sptrsm_solve, ilu0_factor) return STATUS_NOT_SUPPORTED for them, before any other check; so do
    * plan_update_values / plan_detach / spmv_expand / spmv_reduce_rows on a 16-bit plan. */
   SPBLAS_GFX950_F16 = 4, /* IEEE binary16 (torch.float16) */
   SPBLAS_GFX950_BF16 = 5 /* bfloat16 (torch.bfloat16)     */
@@ -117,7 +118,7 @@ int spblas_gfx950_last_hip_error(void);
 /* stream: a hipStream_t (NULL = the null stream), cf. hip_allocator(hipStream_t),
  * vendor/rocsparse/hip_allocator.hpp:22.
  * Graph capture: the execute calls that take a plan or a state whose structure is known (spblas_gfx950_spmv,
- * spblas_gfx950_spmm, spblas_gfx950_sptrsv_solve / _sptrsm_solve, spblas_gfx950_spgemm_numeric after the first fill) only launch kernels
+ * spblas_gfx950_spmm, spblas_gfx950_sptrsv_solve / _sptrsm_solve, spblas_gfx950_ilu0_factor, spblas_gfx950_spgemm_numeric after the first fill) only launch kernels
  * and memsets on this stream and may be recorded with hipStreamBeginCapture and replayed.  Nothing is allocated on a
  * capturing stream: a call that would have to (plan creation, inspect, symbolic passes, the first execute of a plan that
  * sizes a workspace) returns SPBLAS_GFX950_STATUS_NOT_SUPPORTED there -- run it once outside the capture.
@@ -523,6 +524,46 @@ int spblas_gfx950_sptrsm_solve(spblas_gfx950_handle_t handle, spblas_gfx950_trsv
                                int64_t n, const void* alpha, const int32_t* rowptr, const int32_t* colind,
                                const void* values, const void* B, int64_t b_row_stride, int64_t b_col_stride,
                                void* X, int64_t x_row_stride, int64_t x_col_stride, int value_type);
+
+/* ---- incomplete LU on the pattern of A, ILU(0)  (CSR, int32 indices; no reference counterpart) ---------------- */
+/* A is square, m x m.  Preconditions: the columns of every row are strictly ascending and every row stores its diagonal
+ * entry (ilu0_create checks both).  The result LU has A's pattern in ONE array of nnz values: the entries left of the diagonal
+ * are L, whose unit diagonal is implied; the diagonal and the entries right of it are U.  Row by row (IKJ):
+ *     w = row i of A
+ *     for k in the columns of row i with k < i, ascending:    w[k] = w[k] / LU[k][k]
+ *         for j in the columns of row k with j > k, if j is also a column of row i:    w[j] = fma(-w[k], LU[k][j], w[j])
+ *     row i of LU = w
+ * Every entry receives its updates in ascending k, one fma each: the same plan, device and arguments give the same bits on
+ * every call.  No pivoting, no fill, no shift of small pivots.  The storage is what the triangular solves read -- ONE array
+ * serves both, without a copy or a split:
+ *     sptrsv_solve / sptrsm_solve (LOWER, DIAG_UNIT,     LU, b, y)   then   (UPPER, DIAG_EXPLICIT, LU, y, x).
+ *   ilu0_create   the inspect: checks the structure on the device (a row whose columns are not strictly ascending, a column
+ *                 outside [0, m), a row without a stored diagonal or offsets that do not describe nnz entries:
+ *                 STATUS_INVALID_VALUE), records the position of every diagonal entry, and builds the LOWER level plan by
+ *                 calling spblas_gfx950_sptrsv_create -- row i needs exactly the rows k < i with (i, k) in the pattern.  It
+ *                 synchronises the handle's stream more than once -- once for the structure check, which runs before the
+ *                 level builder sees the arrays, then as sptrsv_create does -- (STATUS_NOT_SUPPORTED inside a capture) and
+ *                 allocates everything a factor call needs, the status word included.
+ *   ilu0_factor   a_values == lu_values: in place.  Otherwise A's values are copied to lu_values on the stream first and are
+ *                 never written.  It allocates nothing and synchronises nothing: it enqueues the optional copy, one single-wavefront
+ *                 launch that resets the status word, one launch per wide level and one single-workgroup launch per run of narrow levels, so it
+ *                 may be recorded in a graph from its first call.  rowptr / colind must be the arrays (the same addresses)
+ *                 the plan was made from: anything else is STATUS_PLAN_MISMATCH.
+ *                 Order of checks: C32 / C64 / F16 / BF16 return STATUS_NOT_SUPPORTED before anything else; then handle,
+ *                 pointers, plan against m / nnz / rowptr / colind (STATUS_PLAN_MISMATCH), value type (F32 / F64, else STATUS_INVALID_VALUE).
+ *   pivots        a zero or non-finite pivot does not stop the factorisation: IEEE arithmetic carries on.  ilu0_status
+ *                 synchronises the stream and sets *row to the smallest row index whose final LU[i][i] is zero or not finite
+ *                 in the plan's last factor call, -1 if there is none (or no factor call yet).
+ *   ilu0_info     info[0] levels, [1] widest level, [2] level launches per factor = the plan's launch groups (the reset of the
+ *                 status word and the optional copy come on top), [3] lanes per row. */
+int spblas_gfx950_ilu0_create(spblas_gfx950_handle_t handle, spblas_gfx950_ilu0_t* plan, int64_t m, int64_t nnz,
+                              const int32_t* rowptr, const int32_t* colind);
+int spblas_gfx950_ilu0_destroy(spblas_gfx950_handle_t handle, spblas_gfx950_ilu0_t plan);
+int spblas_gfx950_ilu0_info(spblas_gfx950_ilu0_t plan, int64_t info[4]);
+int spblas_gfx950_ilu0_status(spblas_gfx950_handle_t handle, spblas_gfx950_ilu0_t plan, int64_t* row);
+int spblas_gfx950_ilu0_factor(spblas_gfx950_handle_t handle, spblas_gfx950_ilu0_t plan, int64_t m, int64_t nnz,
+                              const int32_t* rowptr, const int32_t* colind, const void* a_values, void* lu_values,
+                              int value_type);
 
 /* ---- scale:  values[i] *= alpha  (algorithms/scale_impl.hpp:13-19) --------------------------- */
 /* In-place scaling of a matrix's value array or of a dense vector (n elements, device memory).  A SLICED

@@ -916,4 +916,64 @@ void triangular_solve(A&& a, Triangle t, DiagonalStorage d, B&& b, X&& x) {
   triangular_solve(info, a, t, d, b, x);
 }
 
+// ---- ILU(0): incomplete LU on A's own pattern (spblas_gfx950_ilu0_*; no reference counterpart, hence spblas::gfx950) --------
+// A is a plain csr_view (float / double, int32 indices and offsets) with sorted rows and a stored diagonal in every row; LU is
+// a csr_view over A's row offsets and columns with its own value array, or A itself (in place).  LU holds L left of the
+// diagonal (unit diagonal implied) and U on and right of it: the ONE view serves
+//   triangular_solve(lu, lower_triangle, implicit_unit_diagonal, b, y)  and  triangular_solve(lu, upper_triangle, explicit_diagonal, y, x).
+namespace __gfx950 {
+inline ilu0_state_t& ilu0_state_of(operation_info_t& info) {
+  auto* s = dynamic_cast<ilu0_state_t*>(info.state_.get());
+  if (!s) {
+    info.state_ = std::make_unique<ilu0_state_t>();
+    s = static_cast<ilu0_state_t*>(info.state_.get());
+  }
+  return *s;
+}
+template <typename T>
+ilu0_state_t& ilu0_prepare(operation_info_t& info, const csr_view<T, std::int32_t, std::int32_t>& a) {
+  static_assert(std::is_same_v<T, float> || std::is_same_v<T, double>, "ilu0: float / double values only");
+  if (a.shape()[0] != a.shape()[1]) {
+    throw std::invalid_argument("ilu0: matrix dimensions are incompatible.");
+  }
+  auto& st = ilu0_state_of(info);
+  if (!st.matches(a.rowptr().data(), a.colind().data(), a.shape()[0], a.size())) {
+    st.inspect(a.shape()[0], a.size(), a.rowptr().data(), a.colind().data());
+  }
+  return st;
+}
+} // namespace __gfx950
+
+namespace gfx950 {
+template <typename T>
+void ilu0_inspect(operation_info_t& info, const csr_view<T, std::int32_t, std::int32_t>& a) {
+  __gfx950::ilu0_prepare(info, a);
+}
+template <typename T>
+operation_info_t ilu0_inspect(const csr_view<T, std::int32_t, std::int32_t>& a) {
+  operation_info_t info;
+  ilu0_inspect(info, a);
+  return info;
+}
+template <typename T>
+void ilu0(operation_info_t& info, const csr_view<T, std::int32_t, std::int32_t>& a,
+          const csr_view<T, std::int32_t, std::int32_t>& lu) {
+  auto& st = __gfx950::ilu0_prepare(info, a);  // re-analyses only if the pattern changed
+  if (lu.rowptr().data() != a.rowptr().data() || lu.colind().data() != a.colind().data() || lu.size() != a.size() ||
+      lu.shape()[0] != a.shape()[0] || lu.shape()[1] != a.shape()[1]) {
+    throw std::invalid_argument("ilu0: lu must be a view over A's own row offsets and columns.");
+  }
+  st.template factor<T>(a.rowptr().data(), a.colind().data(), a.values().data(), lu.values().data());
+}
+template <typename T>
+void ilu0(const csr_view<T, std::int32_t, std::int32_t>& a, const csr_view<T, std::int32_t, std::int32_t>& lu) {
+  operation_info_t info;
+  ilu0(info, a, lu);
+}
+// synchronises the stream: the smallest row whose pivot was zero or not finite in the last ilu0 call with this info, else -1
+inline std::int64_t ilu0_status(operation_info_t& info) {
+  return __gfx950::ilu0_state_of(info).status();
+}
+} // namespace gfx950
+
 } // namespace spblas

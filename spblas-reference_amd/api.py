@@ -29,14 +29,14 @@ csr_view with int32 column indices (int32 / int64 row offsets), plan-free or ins
 matrix_opt).  Complex operands may be conjugated -- conjugated(A), conjugated(x / B), or a tensor whose lazy conj bit is set
 (t.conj(): the bit is folded into the kernel's flag, nothing is copied) -- and scaled by complex factors: a factor counts
 conjugated iff an odd number of conjugated views wrap it (conjugated(scaled(s, A)) = conj(s) conj(A)).  Everything else with
-complex values -- csc_view / transposed() operands, int64 column indices, SpGEMM, add, transpose, scale, triangular_solve --
-raises TypeError; an output with the conj bit set raises ValueError.
+complex values -- csc_view / transposed() operands, int64 column indices, SpGEMM, add, transpose, scale, triangular_solve,
+ilu0 -- raises TypeError; an output with the conj bit set raises ValueError.
 
 16-bit values: float16 / bfloat16 for SpMV and SpMM on a csr_view with int32 column indices (int32 / int64 row offsets),
 plan-free or inspected (VECTOR / ROWBLOCK / AUTO plans, matrix_opt), scaled() by real factors.  A, x / B and y / C share the
 one 16-bit type; products and sums are formed in fp32 and every output element is rounded once.  Everything else with 16-bit
 values -- csc_view / transposed() operands, int64 column indices, mixed value types, a complex scaled() factor, conjugated
-views, SpGEMM, add, transpose, scale, triangular_solve, the multi-GPU classes -- raises TypeError (conjugated views:
+views, SpGEMM, add, transpose, scale, triangular_solve, ilu0, the multi-GPU classes -- raises TypeError (conjugated views:
 RuntimeError, as for real operands).
 """
 import ctypes
@@ -1623,3 +1623,130 @@ def triangular_solve(*args):
     if sb is not None:  # the solve is linear in b: x = inv(A) (s b) = s inv(A) b
         beta = ct(sb)
         check(_capi.lib().spblas_gfx950_scale(hd.h, x.numel(), ctypes.byref(beta), _ptr(x), vt), "triangular_solve")
+
+
+# --------------------------------------------------------------------------- ILU(0) (no reference counterpart)
+class _Ilu0Plan:
+    """ilu0_inspect state: the lower level plan and the diagonal positions of A's pattern (spblas_gfx950_ilu0_create)."""
+
+    def __init__(self, hd, plan, key, tensors):
+        self.hd, self.plan, self.key, self.tensors = hd, plan, key, tensors
+
+    def info(self):
+        arr = (ctypes.c_int64 * 4)()
+        check(_capi.lib().spblas_gfx950_ilu0_info(self.plan, arr), "spblas_gfx950_ilu0_info")
+        return dict(zip(("levels", "max_level_width", "launches_per_factor", "lanes_per_row"), list(arr)))
+
+    def status(self):
+        row = ctypes.c_int64(-1)
+        hd = _Handle.current(torch.device("cuda", self.hd.device))
+        check(_capi.lib().spblas_gfx950_ilu0_status(hd.h, self.plan, ctypes.byref(row)), "spblas_gfx950_ilu0_status")
+        return int(row.value)
+
+    def __del__(self):
+        try:
+            if self.plan:
+                _capi.lib().spblas_gfx950_ilu0_destroy(self.hd.h, self.plan)
+                self.plan = None
+        except Exception:
+            pass
+
+
+def _ilu0_operand(a, what):
+    """The plain csr_view ILU(0) takes; TypeError for every other operand, dtype or index type."""
+    if not isinstance(a, csr_view):
+        raise TypeError(f"{what}: the operand must be a plain csr_view (scaled, conjugated, transposed and csc_view "
+                        f"operands are not supported), got {type(a).__name__}")
+    vals = a.values()
+    if not _is_tensor(vals) or not _is_tensor(a.rowptr()) or not _is_tensor(a.colind()):
+        raise TypeError(f"{what}: values, row offsets and columns must be tensors")
+    if vals.dtype not in (torch.float32, torch.float64):
+        raise TypeError(f"{what}: float32 / float64 values only, got {vals.dtype}")
+    if a.rowptr().dtype != torch.int32 or a.colind().dtype != torch.int32:
+        raise TypeError(f"{what}: int32 row offsets and columns only, got {a.rowptr().dtype} / {a.colind().dtype}")
+    _check_csr(a, what)
+    m, n = a.shape()
+    if m != n:
+        raise ValueError(f"{what}: matrix dimensions are incompatible (A must be square).")
+    if a.rowptr().numel() < m + 1 or a.colind().numel() < a.size() or vals.numel() < a.size():
+        raise ValueError(f"{what}: the arrays are shorter than the view's shape and size say")
+    return a
+
+
+def _ilu0_key(a):
+    return (a.rowptr().data_ptr(), a.colind().data_ptr(), tuple(a.shape()), a.size())
+
+
+def _ilu0_plan(a):
+    hd = _Handle.current(a.rowptr().device)
+    plan = ctypes.c_void_p()
+    st = _capi.lib().spblas_gfx950_ilu0_create(hd.h, ctypes.byref(plan), a.shape()[0], a.size(), _ptr(a.rowptr()),
+                                               _ptr(a.colind()))
+    if st == _capi.INVALID_VALUE:
+        raise ValueError("ilu0_inspect: every row must hold strictly ascending columns inside [0, m) and its diagonal entry")
+    check(st, "ilu0_inspect")
+    return _Ilu0Plan(hd, plan, _ilu0_key(a), (a.rowptr(), a.colind()))
+
+
+def ilu0_inspect(*args):
+    """ilu0_inspect(a) -> operation_info_t, or ilu0_inspect(info, a): checks A's structure (sorted rows, stored diagonal;
+    ValueError otherwise) and builds the level plan of the factorisation.  Synchronises the stream."""
+    if len(args) == 2:
+        info, a = args
+        ret = False
+    elif len(args) == 1:
+        a, = args
+        info, ret = operation_info_t(), True
+    else:
+        raise TypeError("expected (a) or (info, a)")
+    a = _ilu0_operand(a, "ilu0_inspect")
+    info.state_ = _ilu0_plan(a)
+    return info if ret else None
+
+
+def ilu0(*args):
+    """ilu0(a, lu) / ilu0(info, a, lu): the incomplete LU factorisation of A on A's own pattern, no pivoting (IKJ order, one fma
+    per update: the same bits on every call).  `lu` is a csr_view over A's row offsets and columns with a value tensor of its own,
+    or with A's value tensor (in place; `a` itself may be passed).  Its values hold L left of the diagonal (unit diagonal implied)
+    and U on and right of it: the one view serves triangular_solve(lu, lower_triangle, implicit_unit_diagonal, b, y) and
+    triangular_solve(lu, upper_triangle, explicit_diagonal, y, x).  Nothing is synchronised; ilu0_status(info) tells afterwards
+    whether a pivot was zero or not finite."""
+    if len(args) == 3:
+        info, a, lu = args
+    elif len(args) == 2:
+        a, lu = args
+        info = None
+    else:
+        raise TypeError("expected (a, lu) or (info, a, lu)")
+    a = _ilu0_operand(a, "ilu0")
+    if not isinstance(lu, csr_view):
+        raise TypeError(f"ilu0: lu must be a plain csr_view over A's structure, got {type(lu).__name__}")
+    lv = lu.values()
+    if not _is_tensor(lv) or lv.dtype != a.values().dtype:
+        raise ValueError(f"ilu0: lu's values must have A's value type {a.values().dtype}")
+    if lv.device != a.values().device:
+        raise ValueError("ilu0: lu's values must live on A's device")
+    if lv.numel() < a.size() or lu.size() != a.size() or tuple(lu.shape()) != tuple(a.shape()) or not lv.is_contiguous():
+        raise ValueError("ilu0: lu must have A's shape and a contiguous value array of at least A's number of entries")
+    if lu.rowptr() is None or lu.colind() is None or lu.rowptr().data_ptr() != a.rowptr().data_ptr() or \
+            lu.colind().data_ptr() != a.colind().data_ptr():
+        raise ValueError("ilu0: lu must be a view over A's own row offsets and columns")
+    plan = info.state_ if info is not None and isinstance(info.state_, _Ilu0Plan) else None
+    if plan is None or plan.key != _ilu0_key(a):
+        plan = _ilu0_plan(a)  # no usable inspect result: analyse now
+        if info is not None:
+            info.state_ = plan
+    hd = _Handle.current(a.rowptr().device)
+    vt, _ = _vtype(a.values(), "ilu0")
+    check(_capi.lib().spblas_gfx950_ilu0_factor(hd.h, plan.plan, a.shape()[0], a.size(), _ptr(a.rowptr()), _ptr(a.colind()),
+                                                _ptr(a.values()), _ptr(lv), vt), "ilu0")
+    _note_write(lv)
+
+
+def ilu0_status(info):
+    """The smallest row whose pivot LU[i][i] was zero or not finite in the last ilu0 call on this inspect result, -1 if every
+    pivot was finite and non-zero.  Synchronises the stream."""
+    plan = getattr(info, "state_", None)
+    if not isinstance(plan, _Ilu0Plan):
+        raise TypeError("ilu0_status: expected the operation_info_t of ilu0_inspect / ilu0")
+    return plan.status()
