@@ -75,9 +75,9 @@ typedef enum spblas_gfx950_datatype {
   /* complex, interleaved (re, im) like std::complex<float / double>; alpha / beta point at ONE complex host scalar.
    * SpMV (op N) and SpMM on CSR with int32 columns only: spmv_plan_create (AUTO / VECTOR / ROWBLOCK; SLICED returns
    * STATUS_NOT_SUPPORTED), spblas_gfx950_spmv[_conj], spblas_gfx950_spmm[_strided[_conj]].  The other entry points that take a
-   * value type (spgemm_numeric[_addend], csr_add_numeric, csr_transpose, scale, sptrsv_solve, sptrsm_solve, ilu0_factor) return
-   * STATUS_NOT_SUPPORTED for them, before any other check; so do plan_update_values / plan_detach and the two-stage / multi-GPU calls on a
-   * complex plan. */
+   * value type (spgemm_numeric[_addend], csr_add_numeric, csr_transpose, scale, sptrsv_solve, sptrsm_solve, sptrsv_sweeps,
+   * ilu0_factor) return STATUS_NOT_SUPPORTED for them, before any other check; so do plan_update_values / plan_detach and the
+   * two-stage / multi-GPU calls on a complex plan. */
   SPBLAS_GFX950_C32 = 2, /* std::complex<float>  */
   SPBLAS_GFX950_C64 = 3, /* std::complex<double> */
   /* 16-bit values; alpha / beta point at ONE float each.  Products and sums are formed in fp32 and every output element is
@@ -85,7 +85,7 @@ typedef enum spblas_gfx950_datatype {
    * and SpMM on CSR with int32 columns only: spmv_plan_create (AUTO / VECTOR / ROWBLOCK; AUTO never picks SLICED, SLICED
    * returns STATUS_NOT_SUPPORTED), spblas_gfx950_spmv, spblas_gfx950_spmm[_strided], spmm_inspect.  op = T, the _conj entry
    * points and every other entry point that takes a value type (spgemm_numeric[_addend], csr_add_numeric, csr_transpose,
-   * scale, sptrsv_solve, sptrsm_solve, ilu0_factor) return STATUS_NOT_SUPPORTED for them, before any other check; so do
+   * scale, sptrsv_solve, sptrsm_solve, sptrsv_sweeps, ilu0_factor) return STATUS_NOT_SUPPORTED for them, before any other check; so do
    * plan_update_values / plan_detach / spmv_expand / spmv_reduce_rows on a 16-bit plan. */
   SPBLAS_GFX950_F16 = 4, /* IEEE binary16 (torch.float16) */
   SPBLAS_GFX950_BF16 = 5 /* bfloat16 (torch.bfloat16)     */
@@ -524,6 +524,41 @@ int spblas_gfx950_sptrsm_solve(spblas_gfx950_handle_t handle, spblas_gfx950_trsv
                                int64_t n, const void* alpha, const int32_t* rowptr, const int32_t* colind,
                                const void* values, const void* B, int64_t b_row_stride, int64_t b_col_stride,
                                void* X, int64_t x_row_stride, int64_t x_col_stride, int value_type);
+/* An APPROXIMATE solve by Jacobi sweeps on the triangular system (the iterative sparse triangular solve of Anzt, Chow and
+ * Dongarra; no reference counterpart): what a preconditioner apply needs, at the price of `sweeps + 1` SpMV-shaped launches
+ * instead of one hand-off per level.  The triangle read is the one sptrsv_solve reads (strict part named by uplo, the LAST
+ * stored diagonal entry of a row, none stored: 0; stored diagonals ignored with DIAG_UNIT; columns outside [0, m) ignored).  With
+ *     row(r, v) = (b_r - alpha * sum_{c strictly inside the triangle} a_rc * v_c) / (alpha * d_r)      (no division: DIAG_UNIT)
+ * the iterates are   x0_r = row(r, 0)  -- the sum is taken as 0, nothing is gathered --   and   xk_r = row(r, x(k-1)),
+ * k = 1 .. sweeps: every row reads the PREVIOUS iterate only (Jacobi, not Gauss-Seidel).  x receives x(sweeps).
+ *   fixed point   a row of level l (0-based, as sptrsv_create counts levels) reads rows of lower levels only, so from sweep l
+ *                 on it holds the value of the exact solve and keeps its bits: sweeps >= levels - 1 gives the solution of
+ *                 the triangular system.  Whatever the early iterates of deep rows hold, Inf / NaN included, is overwritten.
+ *   results       the entries of a row are summed in a fixed order given by the lanes per row, which are chosen from nnz / m
+ *                 by the rule of sptrsv_create: the bits of x depend on (m, nnz, the arguments, sweeps) only -- not on
+ *                 whether a plan was passed, nor on what x and work held before.
+ *   buffers       x and work are device vectors of m elements.  Sweep k writes x when sweeps - k is even and work otherwise,
+ *                 so the last sweep lands in x without a copy; sweeps == 0 writes x from b alone.  work holds x(sweeps - 1)
+ *                 afterwards (unspecified with a plan).  The library allocates nothing, synchronises nothing and keeps no
+ *                 pointer between calls: the call may be recorded in a graph from its first use.
+ *   plan          NULL, or a plan of sptrsv_create for the same m / nnz / uplo / diag and the same structure (the structure
+ *                 is the caller's promise, as for sptrsv_solve).  With a plan `sweeps` is clamped to levels - 1 and sweep
+ *                 k >= 2 runs over the rows of level >= k - 1 only (the rows below are final in both buffers) where those
+ *                 are at most a third of the rows; the set is walked in level order, which costs more per row.  The plan is
+ *                 read only: no control words, no status word -- sptrsv_status and a later sptrsv_solve are not affected.
+ *                 Without a plan every sweep covers all m rows and `sweeps` is taken as given.
+ *   checks        in this order: C32 / C64 / F16 / BF16 return STATUS_NOT_SUPPORTED before anything else; handle; pointers
+ *                 (alpha, rowptr, colind / values when nnz > 0, b / x when m > 0; work may be NULL only when sweeps == 0 or
+ *                 m == 0); m, nnz (the limits of sptrsv_create) and sweeps < 0: STATUS_INVALID_SIZE; uplo / diag:
+ *                 STATUS_INVALID_VALUE; a plan whose m / nnz / uplo / diag differ: STATUS_PLAN_MISMATCH; b == x, work == x or
+ *                 work == b (m > 0): STATUS_INVALID_VALUE -- every sweep reads b, and the iterates alternate between x and
+ *                 work; partial overlaps are the caller's error and are not checked; value type (F32 / F64, else
+ *                 STATUS_INVALID_VALUE).  m == 0: success, nothing is launched.
+ *   not offered   a block of right-hand sides, complex and 16-bit values, csc_view operands, several sweeps in one launch. */
+int spblas_gfx950_sptrsv_sweeps(spblas_gfx950_handle_t handle, spblas_gfx950_trsv_t plan /* may be NULL */, int64_t m,
+                                int64_t nnz, int sweeps, int uplo, int diag, const void* alpha, const int32_t* rowptr,
+                                const int32_t* colind, const void* values, const void* b, void* x, void* work,
+                                int value_type);
 
 /* ---- incomplete LU on the pattern of A, ILU(0)  (CSR, int32 indices; no reference counterpart) ---------------- */
 /* A is square, m x m.  Preconditions: the columns of every row are strictly ascending and every row stores its diagonal

@@ -916,6 +916,48 @@ void triangular_solve(A&& a, Triangle t, DiagonalStorage d, B&& b, X&& x) {
   triangular_solve(info, a, t, d, b, x);
 }
 
+// ---- an APPROXIMATE triangular solve by Jacobi sweeps (spblas_gfx950_sptrsv_sweeps; no reference counterpart, hence
+// spblas::gfx950).  x0_r = b_r / d_r, then `sweeps` times x_r = (b_r - the row's strict entries times the PREVIOUS x) / d_r; a
+// row of level l is exact from sweep l on.  Vectors only; b must not be x.  An info that holds the result of
+// triangular_solve_inspect for this matrix, triangle and diagonal narrows the later sweeps to the rows that can still change;
+// any other info, and the overload without one, runs plan-free -- the call never inspects.  The second iterate lives in the
+// info's state (allocated at the first call); the overload without info allocates and frees it around the call. ----------
+namespace gfx950 {
+template <typename A, typename Triangle, typename DiagonalStorage, typename B, typename X>
+  requires(__detail::has_csr_base<A>)
+void triangular_solve_sweeps(operation_info_t& info, A&& a, Triangle, DiagonalStorage, B&& b, X&& x, int sweeps) {
+  static_assert(std::is_same_v<Triangle, upper_triangle_t> || std::is_same_v<Triangle, lower_triangle_t>);
+  static_assert(std::is_same_v<DiagonalStorage, implicit_unit_diagonal_t> ||
+                std::is_same_v<DiagonalStorage, explicit_diagonal_t>);
+  auto ab = __detail::get_ultimate_base(a);
+  auto bb = __detail::get_ultimate_base(b);
+  __gfx950::reject_conjugated(__detail::is_conjugated(a));
+  if (ab.shape()[0] != ab.shape()[1] || static_cast<std::int64_t>(std::ranges::size(x)) != ab.shape()[1] ||
+      static_cast<std::int64_t>(std::ranges::size(bb)) != ab.shape()[0] || sweeps < 0) {
+    throw std::invalid_argument("triangular_solve_sweeps: matrix and vector dimensions are incompatible.");
+  }
+  const int uplo = std::is_same_v<Triangle, upper_triangle_t> ? SPBLAS_GFX950_UPPER : SPBLAS_GFX950_LOWER;
+  const int diag =
+      std::is_same_v<DiagonalStorage, implicit_unit_diagonal_t> ? SPBLAS_GFX950_DIAG_UNIT : SPBLAS_GFX950_DIAG_EXPLICIT;
+  using T = typename decltype(ab)::scalar_type;
+  const T alpha = static_cast<T>(__detail::get_scaling_factor(a).value_or(1.0));
+  const auto beta = __detail::get_scaling_factor(b);
+  auto& st = __gfx950::trsv_state_of(info);
+  st.template sweeps<T>(sweeps, uplo, diag, ab.shape()[0], ab.size(), alpha, ab.rowptr().data(), ab.colind().data(),
+                        ab.values().data(), std::ranges::data(bb), std::ranges::data(x));
+  if (beta.has_value()) {  // the iteration is linear in b: the factor is applied to x afterwards
+    __gfx950::scale_values<T>(st.handle(), static_cast<std::int64_t>(std::ranges::size(x)), static_cast<T>(*beta),
+                              std::ranges::data(x));
+  }
+}
+template <typename A, typename Triangle, typename DiagonalStorage, typename B, typename X>
+  requires(__detail::has_csr_base<A>)
+void triangular_solve_sweeps(A&& a, Triangle t, DiagonalStorage d, B&& b, X&& x, int sweeps) {
+  operation_info_t info;
+  triangular_solve_sweeps(info, a, t, d, b, x, sweeps);
+}
+} // namespace gfx950
+
 // ---- ILU(0): incomplete LU on A's own pattern (spblas_gfx950_ilu0_*; no reference counterpart, hence spblas::gfx950) --------
 // A is a plain csr_view (float / double, int32 indices and offsets) with sorted rows and a stored diagonal in every row; LU is
 // a csr_view over A's row offsets and columns with its own value array, or A itself (in place).  LU holds L left of the

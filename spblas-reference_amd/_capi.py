@@ -119,6 +119,9 @@ PROTOTYPES = [
     ("spblas_gfx950_sptrsm_solve", c_int,
      [c_void_p, c_void_p, c_i64, c_i64, c_i64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_i64, c_void_p,
       c_i64, c_i64, c_int]),
+    ("spblas_gfx950_sptrsv_sweeps", c_int,
+     [c_void_p, c_void_p, c_i64, c_i64, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+      c_void_p, c_int]),
     ("spblas_gfx950_ilu0_create", c_int, [c_void_p, ctypes.POINTER(c_void_p), c_i64, c_i64, c_void_p, c_void_p]),
     ("spblas_gfx950_ilu0_destroy", c_int, [c_void_p, c_void_p]),
     ("spblas_gfx950_ilu0_info", c_int, [c_void_p, ctypes.POINTER(c_i64)]),

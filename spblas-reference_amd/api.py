@@ -30,14 +30,14 @@ matrix_opt).  Complex operands may be conjugated -- conjugated(A), conjugated(x 
 (t.conj(): the bit is folded into the kernel's flag, nothing is copied) -- and scaled by complex factors: a factor counts
 conjugated iff an odd number of conjugated views wrap it (conjugated(scaled(s, A)) = conj(s) conj(A)).  Everything else with
 complex values -- csc_view / transposed() operands, int64 column indices, SpGEMM, add, transpose, scale, triangular_solve,
-ilu0 -- raises TypeError; an output with the conj bit set raises ValueError.
+triangular_solve_sweeps, ilu0 -- raises TypeError; an output with the conj bit set raises ValueError.
 
 16-bit values: float16 / bfloat16 for SpMV and SpMM on a csr_view with int32 column indices (int32 / int64 row offsets),
 plan-free or inspected (VECTOR / ROWBLOCK / AUTO plans, matrix_opt), scaled() by real factors.  A, x / B and y / C share the
 one 16-bit type; products and sums are formed in fp32 and every output element is rounded once.  Everything else with 16-bit
 values -- csc_view / transposed() operands, int64 column indices, mixed value types, a complex scaled() factor, conjugated
-views, SpGEMM, add, transpose, scale, triangular_solve, ilu0, the multi-GPU classes -- raises TypeError (conjugated views:
-RuntimeError, as for real operands).
+views, SpGEMM, add, transpose, scale, triangular_solve, triangular_solve_sweeps, ilu0, the multi-GPU classes -- raises
+TypeError (conjugated views: RuntimeError, as for real operands).
 """
 import ctypes
 import threading
@@ -1623,6 +1623,53 @@ def triangular_solve(*args):
     if sb is not None:  # the solve is linear in b: x = inv(A) (s b) = s inv(A) b
         beta = ct(sb)
         check(_capi.lib().spblas_gfx950_scale(hd.h, x.numel(), ctypes.byref(beta), _ptr(x), vt), "triangular_solve")
+
+
+def triangular_solve_sweeps(*args):
+    """triangular_solve_sweeps(a, uplo, diag, b, x, sweeps) / triangular_solve_sweeps(info, a, uplo, diag, b, x, sweeps): an
+    APPROXIMATE x = inv(A) b by Jacobi sweeps on the triangle triangular_solve reads (spblas_gfx950_sptrsv_sweeps; no reference
+    counterpart).  x0_r = b_r / d_r, then `sweeps` times x_r = (b_r - sum of the row's strict entries times the PREVIOUS x) /
+    d_r: one SpMV-shaped launch per sweep and no hand-off between levels -- what a preconditioner apply wants.  A row of level
+    l is exact from sweep l on, so sweeps >= levels - 1 is the solve itself.  Operands as for triangular_solve with vectors
+    (csr_view, float32 / float64, int32 offsets and columns, scaled(a), scaled(b)).  An info of triangular_solve_inspect for
+    this matrix, triangle and diagonal narrows the later sweeps to the rows that can still change; without one every sweep
+    covers all rows -- the call never inspects by itself.  The bits of x are the same either way.  A block of right-hand sides
+    (2-D b / x) raises NotImplementedError."""
+    if len(args) == 7:
+        info, a, uplo, diag, b, x, sweeps = args
+    elif len(args) == 6:
+        a, uplo, diag, b, x, sweeps = args
+        info = None
+    else:
+        raise TypeError("expected (a, uplo, diag, b, x, sweeps) or (info, a, uplo, diag, b, x, sweeps)")
+    bb = get_ultimate_base(b)
+    if (_is_tensor(bb) and bb.dim() == 2) or (_is_tensor(x) and x.dim() == 2):
+        raise NotImplementedError("gfx950 triangular_solve_sweeps: vectors only (a block of right-hand sides is not offered)")
+    a_base = _trsv_operands(a, uplo, diag, b, x)
+    if isinstance(sweeps, bool) or not isinstance(sweeps, int):
+        raise TypeError("triangular_solve_sweeps: sweeps must be an int")
+    if sweeps < 0 or sweeps > 2 ** 31 - 1:
+        raise ValueError("triangular_solve_sweeps: sweeps must be a non-negative int")
+    plan = info.state_ if info is not None and isinstance(info.state_, _TrsvPlan) else None
+    if plan is not None and plan.key != _trsv_key(a_base, uplo, diag):
+        plan = None  # another matrix, triangle or diagonal: plan-free (never a hidden inspect)
+    hd = _Handle.current(a_base.rowptr().device)
+    vt, ct = _vtype(a_base.values(), "triangular_solve_sweeps")
+    sa = get_scaling_factor(a)
+    alpha = ct(1 if sa is None else sa)
+    sb = get_scaling_factor(b)
+    if bb.numel() > 0 and bb.untyped_storage().data_ptr() == x.untyped_storage().data_ptr():
+        bb = bb.clone()  # every sweep reads b while the iterates alternate between x and the work vector
+    work = torch.empty_like(x) if sweeps > 0 else None
+    check(_capi.lib().spblas_gfx950_sptrsv_sweeps(
+        hd.h, plan.plan if plan is not None else None, a_base.shape()[0], a_base.size(), sweeps,
+        _capi.UPPER if isinstance(uplo, upper_triangle_t) else _capi.LOWER,
+        _capi.DIAG_UNIT if isinstance(diag, implicit_unit_diagonal_t) else _capi.DIAG_EXPLICIT, ctypes.byref(alpha),
+        _ptr(a_base.rowptr()), _ptr(a_base.colind()), _ptr(a_base.values()), _ptr(bb), _ptr(x), _ptr(work), vt),
+        "triangular_solve_sweeps")
+    if sb is not None:  # the iteration is linear in b: sweeps(s b) = s sweeps(b)
+        beta = ct(sb)
+        check(_capi.lib().spblas_gfx950_scale(hd.h, x.numel(), ctypes.byref(beta), _ptr(x), vt), "triangular_solve_sweeps")
 
 
 # --------------------------------------------------------------------------- ILU(0) (no reference counterpart)

@@ -22,6 +22,7 @@ void preload_spgemm();
 void preload_transpose();
 void preload_sptrsv();
 void preload_sptrsm();
+void preload_sptrsv_sweeps();
 void preload_ilu0();
 void preload_multigpu();
 } // namespace spb
@@ -85,6 +86,7 @@ int spblas_gfx950_create(spblas_gfx950_handle_t* handle, void* stream) {
       spb::preload_transpose();
       spb::preload_sptrsv();
       spb::preload_sptrsm();
+      spb::preload_sptrsv_sweeps();
       spb::preload_ilu0();
       spb::preload_multigpu();
     });
