@@ -76,7 +76,7 @@ typedef enum spblas_gfx950_datatype {
    * SpMV (op N) and SpMM on CSR with int32 columns only: spmv_plan_create (AUTO / VECTOR / ROWBLOCK; SLICED returns
    * STATUS_NOT_SUPPORTED), spblas_gfx950_spmv[_conj], spblas_gfx950_spmm[_strided[_conj]].  The other entry points that take a
    * value type (spgemm_numeric[_addend], csr_add_numeric, csr_transpose, scale, sptrsv_solve, sptrsm_solve, sptrsv_sweeps,
-   * ilu0_factor) return STATUS_NOT_SUPPORTED for them, before any other check; so do plan_update_values / plan_detach and the
+   * ilu0_factor, ilu0_sweeps) return STATUS_NOT_SUPPORTED for them, before any other check; so do plan_update_values / plan_detach and the
    * two-stage / multi-GPU calls on a complex plan. */
   SPBLAS_GFX950_C32 = 2, /* std::complex<float>  */
   SPBLAS_GFX950_C64 = 3, /* std::complex<double> */
@@ -85,8 +85,8 @@ typedef enum spblas_gfx950_datatype {
    * and SpMM on CSR with int32 columns only: spmv_plan_create (AUTO / VECTOR / ROWBLOCK; AUTO never picks SLICED, SLICED
    * returns STATUS_NOT_SUPPORTED), spblas_gfx950_spmv, spblas_gfx950_spmm[_strided], spmm_inspect.  op = T, the _conj entry
    * points and every other entry point that takes a value type (spgemm_numeric[_addend], csr_add_numeric, csr_transpose,
-   * scale, sptrsv_solve, sptrsm_solve, sptrsv_sweeps, ilu0_factor) return STATUS_NOT_SUPPORTED for them, before any other check; so do
-   * plan_update_values / plan_detach / spmv_expand / spmv_reduce_rows on a 16-bit plan. */
+   * scale, sptrsv_solve, sptrsm_solve, sptrsv_sweeps, ilu0_factor, ilu0_sweeps) return STATUS_NOT_SUPPORTED for them,
+   * before any other check; so do plan_update_values / plan_detach / spmv_expand / spmv_reduce_rows on a 16-bit plan. */
   SPBLAS_GFX950_F16 = 4, /* IEEE binary16 (torch.float16) */
   SPBLAS_GFX950_BF16 = 5 /* bfloat16 (torch.bfloat16)     */
 } spblas_gfx950_datatype;
@@ -118,7 +118,7 @@ int spblas_gfx950_last_hip_error(void);
 /* stream: a hipStream_t (NULL = the null stream), cf. hip_allocator(hipStream_t),
  * vendor/rocsparse/hip_allocator.hpp:22.
  * Graph capture: the execute calls that take a plan or a state whose structure is known (spblas_gfx950_spmv,
- * spblas_gfx950_spmm, spblas_gfx950_sptrsv_solve / _sptrsm_solve, spblas_gfx950_ilu0_factor, spblas_gfx950_spgemm_numeric after the first fill) only launch kernels
+ * spblas_gfx950_spmm, spblas_gfx950_sptrsv_solve / _sptrsm_solve, spblas_gfx950_ilu0_factor / _ilu0_sweeps, spblas_gfx950_spgemm_numeric after the first fill) only launch kernels
  * and memsets on this stream and may be recorded with hipStreamBeginCapture and replayed.  Nothing is allocated on a
  * capturing stream: a call that would have to (plan creation, inspect, symbolic passes, the first execute of a plan that
  * sizes a workspace) returns SPBLAS_GFX950_STATUS_NOT_SUPPORTED there -- run it once outside the capture.
@@ -598,6 +598,38 @@ int spblas_gfx950_ilu0_info(spblas_gfx950_ilu0_t plan, int64_t info[4]);
 int spblas_gfx950_ilu0_status(spblas_gfx950_handle_t handle, spblas_gfx950_ilu0_t plan, int64_t* row);
 int spblas_gfx950_ilu0_factor(spblas_gfx950_handle_t handle, spblas_gfx950_ilu0_t plan, int64_t m, int64_t nnz,
                               const int32_t* rowptr, const int32_t* colind, const void* a_values, void* lu_values,
+                              int value_type);
+/* ILU(0) by fixed-point sweeps: an APPROXIMATE factor without one hand-off per level (the fine-grained parallel ILU of Chow and
+ * Patel, SIAM J. Sci. Comput. 37(2), 2015, in row form; no reference counterpart).  With LU(0) = A, for k = 1 .. sweeps every
+ * row i independently runs the sequence of ilu0_factor on a copy of A's row, reading the PREVIOUS iterate only:
+ *     w = row i of A
+ *     for c in the columns of row i with c < i, ascending:    w[c] = w[c] / LU(k-1)[c][c]
+ *         for j in the columns of row c with j > c, if j is also a column of row i:    w[j] = fma(-w[c], LU(k-1)[c][j], w[j])
+ *     row i of LU(k) = w
+ * Inside a row the elimination is exact; across rows it is Jacobi.  One launch per sweep, all m rows in index order.
+ *   fixed point   a row of level l (0-based, in the LOWER level plan of ilu0_create; ilu0_info's info[0] counts the levels) reads
+ *                 rows of lower levels only, so from sweep l on it holds the bits of ilu0_factor, whatever Inf / NaN the earlier
+ *                 iterates carried: sweeps >= levels - 1 IS ilu0_factor, bit for bit.  `sweeps` is clamped to
+ *                 max(1, levels - 1).
+ *   results       the bits of LU depend on (A, the pattern, sweeps) alone -- not on the lanes per row, the grid or on what
+ *                 lu_values and work held before.
+ *   buffers       lu_values and work are device arrays of nnz values.  Sweep 1 reads A as the previous iterate (no copy);
+ *                 with s = the clamped count, sweep k writes lu_values when s - k is even and work otherwise, so the last
+ *                 sweep lands in lu_values.  a_values is never written; work is unspecified afterwards.  Nothing is
+ *                 allocated and nothing synchronised: the call enqueues the single-wavefront reset of the status word and
+ *                 one launch per sweep, and may be recorded in a graph from its first use.
+ *   pivots        only the LAST sweep checks its final diagonal and raises the plan's status word: ilu0_status afterwards
+ *                 reports on LU(s) as it does on the factor of ilu0_factor.  ilu0_info is unchanged.
+ *   checks        in this order: C32 / C64 / F16 / BF16 return STATUS_NOT_SUPPORTED before anything else; handle; pointers
+ *                 (plan, rowptr, colind / a_values / lu_values when nnz > 0, work when nnz > 0 and the REQUESTED sweeps >= 2);
+ *                 plan against m / nnz / rowptr / colind (the same addresses): STATUS_PLAN_MISMATCH; value type (F32 / F64,
+ *                 else STATUS_INVALID_VALUE); sweeps < 1: STATUS_INVALID_VALUE; a_values == lu_values, a_values == work or
+ *                 lu_values == work: STATUS_INVALID_VALUE -- every sweep re-reads A, so there is no in-place form; partial
+ *                 overlaps are the caller's error and are not checked.  m == 0: success, nothing is launched.
+ *   not offered   an active-row set per sweep, a block of matrices, complex and 16-bit values, csc_view operands, several
+ *                 sweeps in one launch, scaling A to a unit diagonal first (the caller's, with spblas_gfx950_scale). */
+int spblas_gfx950_ilu0_sweeps(spblas_gfx950_handle_t handle, spblas_gfx950_ilu0_t plan, int64_t m, int64_t nnz, int sweeps,
+                              const int32_t* rowptr, const int32_t* colind, const void* a_values, void* lu_values, void* work,
                               int value_type);
 
 /* ---- scale:  values[i] *= alpha  (algorithms/scale_impl.hpp:13-19) --------------------------- */

@@ -1012,6 +1012,37 @@ void ilu0(const csr_view<T, std::int32_t, std::int32_t>& a, const csr_view<T, st
   operation_info_t info;
   ilu0(info, a, lu);
 }
+// An APPROXIMATE ilu0 by fixed-point sweeps (spblas_gfx950_ilu0_sweeps): LU(0) = A, then `sweeps` times every row runs ilu0's
+// elimination on A's row with the pivots and pivot rows of the PREVIOUS iterate.  A row of level l has ilu0's bits from sweep l
+// on: sweeps >= levels - 1 IS ilu0.  a, lu and work (at least a.size() elements; may be empty when sweeps == 1) are three
+// different value arrays -- there is no in-place form.
+template <typename T>
+void ilu0_sweeps(operation_info_t& info, const csr_view<T, std::int32_t, std::int32_t>& a,
+                 const csr_view<T, std::int32_t, std::int32_t>& lu, std::type_identity_t<std::span<T>> work, int sweeps) {
+  if (lu.rowptr().data() != a.rowptr().data() || lu.colind().data() != a.colind().data() || lu.size() != a.size() ||
+      lu.shape()[0] != a.shape()[0] || lu.shape()[1] != a.shape()[1]) {
+    throw std::invalid_argument("ilu0_sweeps: lu must be a view over A's own row offsets and columns.");
+  }
+  if (sweeps < 1) {
+    throw std::invalid_argument("ilu0_sweeps: sweeps must be at least 1.");
+  }
+  if (sweeps >= 2 && work.size() < static_cast<std::size_t>(a.size())) {
+    throw std::invalid_argument("ilu0_sweeps: work must hold at least A's number of entries.");
+  }
+  if (a.size() > 0 && (lu.values().data() == a.values().data() ||
+                       (!work.empty() && (work.data() == a.values().data() || work.data() == lu.values().data())))) {
+    throw std::invalid_argument("ilu0_sweeps: a, lu and work must be three different value arrays (no in-place form).");
+  }
+  auto& st = __gfx950::ilu0_prepare(info, a);  // after the argument checks; re-analyses only if the pattern changed
+  st.template sweeps<T>(sweeps, a.rowptr().data(), a.colind().data(), a.values().data(), lu.values().data(),
+                        work.empty() ? nullptr : work.data());
+}
+template <typename T>
+void ilu0_sweeps(const csr_view<T, std::int32_t, std::int32_t>& a, const csr_view<T, std::int32_t, std::int32_t>& lu,
+                 std::type_identity_t<std::span<T>> work, int sweeps) {
+  operation_info_t info;
+  ilu0_sweeps(info, a, lu, work, sweeps);
+}
 // synchronises the stream: the smallest row whose pivot was zero or not finite in the last ilu0 call with this info, else -1
 inline std::int64_t ilu0_status(operation_info_t& info) {
   return __gfx950::ilu0_state_of(info).status();

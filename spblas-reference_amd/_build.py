@@ -105,7 +105,7 @@ def build_rccl_test(force=False):
     return RCCL_TEST_BIN
 
 
-EXAMPLES = ["device_spmv", "device_spgemm", "device_sptrsv", "device_sptrsm", "device_ilu0", "device_sptrsv_sweeps"]
+EXAMPLES = ["device_spmv", "device_spgemm", "device_sptrsv", "device_sptrsm", "device_ilu0", "device_sptrsv_sweeps", "device_ilu0_sweeps"]
 
 
 def build_examples(force=False):

@@ -127,6 +127,8 @@ PROTOTYPES = [
     ("spblas_gfx950_ilu0_info", c_int, [c_void_p, ctypes.POINTER(c_i64)]),
     ("spblas_gfx950_ilu0_status", c_int, [c_void_p, c_void_p, ctypes.POINTER(c_i64)]),
     ("spblas_gfx950_ilu0_factor", c_int, [c_void_p, c_void_p, c_i64, c_i64, c_void_p, c_void_p, c_void_p, c_void_p, c_int]),
+    ("spblas_gfx950_ilu0_sweeps", c_int,
+     [c_void_p, c_void_p, c_i64, c_i64, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int]),
     ("spblas_gfx950_spgemm_set_addend", c_int, [c_void_p, c_void_p, c_i64, c_void_p, c_void_p]),
     ("spblas_gfx950_spgemm_numeric_addend", c_int,
      [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,

@@ -30,13 +30,13 @@ matrix_opt).  Complex operands may be conjugated -- conjugated(A), conjugated(x 
 (t.conj(): the bit is folded into the kernel's flag, nothing is copied) -- and scaled by complex factors: a factor counts
 conjugated iff an odd number of conjugated views wrap it (conjugated(scaled(s, A)) = conj(s) conj(A)).  Everything else with
 complex values -- csc_view / transposed() operands, int64 column indices, SpGEMM, add, transpose, scale, triangular_solve,
-triangular_solve_sweeps, ilu0 -- raises TypeError; an output with the conj bit set raises ValueError.
+triangular_solve_sweeps, ilu0, ilu0_sweeps -- raises TypeError; an output with the conj bit set raises ValueError.
 
 16-bit values: float16 / bfloat16 for SpMV and SpMM on a csr_view with int32 column indices (int32 / int64 row offsets),
 plan-free or inspected (VECTOR / ROWBLOCK / AUTO plans, matrix_opt), scaled() by real factors.  A, x / B and y / C share the
 one 16-bit type; products and sums are formed in fp32 and every output element is rounded once.  Everything else with 16-bit
 values -- csc_view / transposed() operands, int64 column indices, mixed value types, a complex scaled() factor, conjugated
-views, SpGEMM, add, transpose, scale, triangular_solve, triangular_solve_sweeps, ilu0, the multi-GPU classes -- raises
+views, SpGEMM, add, transpose, scale, triangular_solve, triangular_solve_sweeps, ilu0, ilu0_sweeps, the multi-GPU classes -- raises
 TypeError (conjugated views: RuntimeError, as for real operands).
 """
 import ctypes
@@ -1751,6 +1751,33 @@ def ilu0_inspect(*args):
     return info if ret else None
 
 
+def _ilu0_lu_values(a, lu, what):
+    """The value tensor of `lu`, a csr_view over A's own row offsets and columns."""
+    if not isinstance(lu, csr_view):
+        raise TypeError(f"{what}: lu must be a plain csr_view over A's structure, got {type(lu).__name__}")
+    lv = lu.values()
+    if not _is_tensor(lv) or lv.dtype != a.values().dtype:
+        raise ValueError(f"{what}: lu's values must have A's value type {a.values().dtype}")
+    if lv.device != a.values().device:
+        raise ValueError(f"{what}: lu's values must live on A's device")
+    if lv.numel() < a.size() or lu.size() != a.size() or tuple(lu.shape()) != tuple(a.shape()) or not lv.is_contiguous():
+        raise ValueError(f"{what}: lu must have A's shape and a contiguous value array of at least A's number of entries")
+    if lu.rowptr() is None or lu.colind() is None or lu.rowptr().data_ptr() != a.rowptr().data_ptr() or \
+            lu.colind().data_ptr() != a.colind().data_ptr():
+        raise ValueError(f"{what}: lu must be a view over A's own row offsets and columns")
+    return lv
+
+
+def _ilu0_plan_of(info, a):
+    """The inspect result in `info` if it is this pattern's, else a new one (stored into `info`)."""
+    plan = info.state_ if info is not None and isinstance(info.state_, _Ilu0Plan) else None
+    if plan is None or plan.key != _ilu0_key(a):
+        plan = _ilu0_plan(a)  # no usable inspect result: analyse now
+        if info is not None:
+            info.state_ = plan
+    return plan
+
+
 def ilu0(*args):
     """ilu0(a, lu) / ilu0(info, a, lu): the incomplete LU factorisation of A on A's own pattern, no pivoting (IKJ order, one fma
     per update: the same bits on every call).  `lu` is a csr_view over A's row offsets and columns with a value tensor of its own,
@@ -1766,28 +1793,60 @@ def ilu0(*args):
     else:
         raise TypeError("expected (a, lu) or (info, a, lu)")
     a = _ilu0_operand(a, "ilu0")
-    if not isinstance(lu, csr_view):
-        raise TypeError(f"ilu0: lu must be a plain csr_view over A's structure, got {type(lu).__name__}")
-    lv = lu.values()
-    if not _is_tensor(lv) or lv.dtype != a.values().dtype:
-        raise ValueError(f"ilu0: lu's values must have A's value type {a.values().dtype}")
-    if lv.device != a.values().device:
-        raise ValueError("ilu0: lu's values must live on A's device")
-    if lv.numel() < a.size() or lu.size() != a.size() or tuple(lu.shape()) != tuple(a.shape()) or not lv.is_contiguous():
-        raise ValueError("ilu0: lu must have A's shape and a contiguous value array of at least A's number of entries")
-    if lu.rowptr() is None or lu.colind() is None or lu.rowptr().data_ptr() != a.rowptr().data_ptr() or \
-            lu.colind().data_ptr() != a.colind().data_ptr():
-        raise ValueError("ilu0: lu must be a view over A's own row offsets and columns")
-    plan = info.state_ if info is not None and isinstance(info.state_, _Ilu0Plan) else None
-    if plan is None or plan.key != _ilu0_key(a):
-        plan = _ilu0_plan(a)  # no usable inspect result: analyse now
-        if info is not None:
-            info.state_ = plan
+    lv = _ilu0_lu_values(a, lu, "ilu0")
+    plan = _ilu0_plan_of(info, a)
     hd = _Handle.current(a.rowptr().device)
     vt, _ = _vtype(a.values(), "ilu0")
     check(_capi.lib().spblas_gfx950_ilu0_factor(hd.h, plan.plan, a.shape()[0], a.size(), _ptr(a.rowptr()), _ptr(a.colind()),
                                                 _ptr(a.values()), _ptr(lv), vt), "ilu0")
     _note_write(lv)
+
+
+def ilu0_sweeps(*args):
+    """ilu0_sweeps(a, lu, work, sweeps) / ilu0_sweeps(info, a, lu, work, sweeps): an APPROXIMATE ilu0 by fixed-point sweeps
+    (spblas_gfx950_ilu0_sweeps; the row form of Chow and Patel's fine-grained ILU; no reference counterpart).  LU(0) = A, then
+    `sweeps` times every row runs ilu0's elimination on A's row with the pivots and pivot rows of the PREVIOUS iterate: one
+    launch per sweep and no hand-off between levels.  A row of level l has ilu0's bits from sweep l on, so sweeps >= levels - 1
+    IS ilu0 (the count is clamped there).  Operands as for ilu0, but `lu` must own its values -- every sweep re-reads A, so there
+    is no in-place form (ValueError).  `work` is a contiguous tensor of A's dtype and device with at least a.size() elements
+    (unspecified afterwards), or None when sweeps <= 1.  Nothing is synchronised; ilu0_status(info) reports on the final
+    pivots of the last sweep.  Without a usable inspect result the call analyses as ilu0 does."""
+    if len(args) == 5:
+        info, a, lu, work, sweeps = args
+    elif len(args) == 4:
+        a, lu, work, sweeps = args
+        info = None
+    else:
+        raise TypeError("expected (a, lu, work, sweeps) or (info, a, lu, work, sweeps)")
+    a = _ilu0_operand(a, "ilu0_sweeps")
+    lv = _ilu0_lu_values(a, lu, "ilu0_sweeps")
+    if isinstance(sweeps, bool) or not isinstance(sweeps, int):
+        raise TypeError("ilu0_sweeps: sweeps must be an int")
+    if sweeps < 1 or sweeps > 2 ** 31 - 1:
+        raise ValueError("ilu0_sweeps: sweeps must be a positive int")
+    av = a.values()
+    if a.size() > 0 and lv.data_ptr() == av.data_ptr():
+        raise ValueError("ilu0_sweeps: lu must own its values (every sweep re-reads A: there is no in-place form)")
+    if work is None:
+        if sweeps > 1:
+            raise ValueError("ilu0_sweeps: work may be None only when sweeps <= 1")
+    else:
+        if not _is_tensor(work):
+            raise TypeError(f"ilu0_sweeps: work must be a tensor or None, got {type(work).__name__}")
+        if work.dtype != av.dtype or work.device != av.device:
+            raise ValueError(f"ilu0_sweeps: work must have A's value type {av.dtype} and live on A's device")
+        if work.numel() < a.size() or not work.is_contiguous():
+            raise ValueError("ilu0_sweeps: work must be contiguous and hold at least A's number of entries")
+        if a.size() > 0 and work.data_ptr() in (av.data_ptr(), lv.data_ptr()):
+            raise ValueError("ilu0_sweeps: work must be a buffer of its own, neither A's values nor lu's")
+    plan = _ilu0_plan_of(info, a)
+    hd = _Handle.current(a.rowptr().device)
+    vt, _ = _vtype(av, "ilu0_sweeps")
+    check(_capi.lib().spblas_gfx950_ilu0_sweeps(hd.h, plan.plan, a.shape()[0], a.size(), sweeps, _ptr(a.rowptr()),
+                                                _ptr(a.colind()), _ptr(av), _ptr(lv), _ptr(work), vt), "ilu0_sweeps")
+    _note_write(lv)
+    if work is not None:
+        _note_write(work)
 
 
 def ilu0_status(info):

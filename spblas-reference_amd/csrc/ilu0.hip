@@ -30,11 +30,15 @@
 // Hand-off of LU inside a launch (the single-workgroup kernel walks many levels): every LU value is stored write-through at
 // agent scope and every load of LU is an agent-scope load, as sptrsm.hip does for X; rowptr, colind and the plan's arrays are
 // never written and are read with plain loads.
+//
+// The same factor by fixed-point sweeps (spblas_gfx950_ilu0_sweeps, further down): one launch per sweep over all rows, every row
+// from the previous iterate, no hand-off between levels; levels - 1 sweeps give the bits of the schedule above.
 #include "common.hpp"
 #include "complex_api.hpp"
 #include "lowp_api.hpp"
 #include "trsv_plan.hpp"
 
+#include <algorithm>
 #include <cstdint>
 #include <new>
 
@@ -193,6 +197,120 @@ __global__ __launch_bounds__(ILU0_CHAIN_THREADS) void ilu0_chain_kernel(int l0, 
   }
 }
 
+// ---- ILU(0) by fixed-point sweeps (spblas_gfx950_ilu0_sweeps; the row form of Chow and Patel, SIAM J. Sci. Comput. 37(2)) ----
+// LU(0) = A; sweep k: every row runs ilu0_row's sequence on a copy of A's row, with the pivot values and pivot rows taken from
+// the PREVIOUS iterate -- exact elimination inside a row, Jacobi across rows.  A row of level l reads rows of lower levels only, so
+// it has ilu0's bits from sweep l on.  prev, next and A are different buffers (sweep 1: prev IS A) and a sweep ends at a kernel
+// boundary: every load of A and prev is a plain load, every store of the fast path a plain store.
+template <typename T>
+struct ilu0_sweep_args {
+  const int32_t* rowptr;
+  const int32_t* colind;
+  const int32_t* diag;
+  const T* a;     // A's values: the start of every row in every sweep
+  const T* prev;  // the previous iterate: pivots and pivot rows
+  T* next;        // this sweep's iterate
+  unsigned* status;
+  int m, G;
+  int last;  // the last sweep checks the final pivots
+};
+
+// One row of one sweep, by its team.  The fast path keeps columns and working values in the team's LDS slice and stores the whole
+// row, lower part included, at the end; the long path works in the row's own slice of `next`, seeded with A's row, with the
+// agent-scope accesses and the drain of ilu0_row's long path (only this team touches that slice).
+template <typename T>
+__device__ __forceinline__ void ilu0_sweep_row(const ilu0_sweep_args<T>& a, int r, int t, int* wc, T* wv) {
+  const int G = a.G;
+  const int p0 = a.rowptr[r], len = a.rowptr[r + 1] - p0;
+  const int dq = a.diag[r] - p0;
+  if (len <= G * ILU0_LDS_PER_LANE) {
+    for (int e = t; e < len; e += G) {
+      wc[e] = a.colind[p0 + e];
+      wv[e] = a.a[p0 + e];
+    }
+    ilu0_step_lds();
+    for (int q = 0; q < dq; ++q) {
+      const int k = wc[q];
+      const int kd = a.diag[k], k1 = a.rowptr[k + 1];
+      const T mult = wv[q] / a.prev[kd];
+      for (int p = kd + 1 + t; p < k1; p += G) {
+        const int c = a.colind[p];
+        const T u = a.prev[p];
+        int lo = q + 1, hi = len;
+        while (lo < hi) {
+          const int mid = (lo + hi) >> 1;
+          if (wc[mid] < c)
+            lo = mid + 1;
+          else
+            hi = mid;
+        }
+        if (lo < len && wc[lo] == c)
+          wv[lo] = ilu0_fma(-mult, u, wv[lo]);
+      }
+      // every lane of the team read wv[q] above in ONE instruction of the wavefront, issued before this store (LDS operations of
+      // a wavefront complete in order), so the store cannot reach a lane's read of the dividend; the next step reads it divided
+      if (t == 0)
+        wv[q] = mult;  // final: later steps touch positions right of q only
+      ilu0_step_lds();
+    }
+    for (int e = t; e < len; e += G)
+      a.next[p0 + e] = wv[e];
+    if (a.last && t == 0) {
+      const T d = wv[dq];
+      if (!(d != T(0)) || !(d - d == T(0)))
+        atomicMax(a.status, 0xFFFFFFFFu - (unsigned) r);
+    }
+  } else {
+    const int32_t* rc = a.colind + p0;
+    T* rv = a.next + p0;
+    for (int e = t; e < len; e += G)
+      ilu0_st(rv + e, a.a[p0 + e]);
+    ilu0_step_global();
+    for (int q = 0; q < dq; ++q) {
+      const int k = rc[q];
+      const int kd = a.diag[k], k1 = a.rowptr[k + 1];
+      const T mult = ilu0_ld(rv + q) / a.prev[kd];
+      for (int p = kd + 1 + t; p < k1; p += G) {
+        const int c = a.colind[p];
+        const T u = a.prev[p];
+        int lo = q + 1, hi = len;
+        while (lo < hi) {
+          const int mid = (lo + hi) >> 1;
+          if (rc[mid] < c)
+            lo = mid + 1;
+          else
+            hi = mid;
+        }
+        if (lo < len && rc[lo] == c)
+          ilu0_st(rv + lo, ilu0_fma(-mult, u, ilu0_ld(rv + lo)));
+      }
+      // as in the fast path: the team's loads of rv[q] above were one instruction, issued (and, feeding the division, returned)
+      // before lane 0 reaches this store
+      if (t == 0)
+        ilu0_st(rv + q, mult);
+      ilu0_step_global();
+    }
+    if (a.last && t == 0) {
+      const T d = ilu0_ld(rv + dq);
+      if (!(d != T(0)) || !(d - d == T(0)))
+        atomicMax(a.status, 0xFFFFFFFFu - (unsigned) r);
+    }
+  }
+}
+
+// one sweep: all m rows in index order, one team per row
+template <typename T>
+__global__ __launch_bounds__(ILU0_LEVEL_THREADS) void ilu0_sweep_kernel(ilu0_sweep_args<T> a) {
+  __shared__ int s_cols[ILU0_LEVEL_THREADS * ILU0_LDS_PER_LANE];
+  __shared__ T s_vals[ILU0_LEVEL_THREADS * ILU0_LDS_PER_LANE];
+  const int team = (int) threadIdx.x / a.G;
+  const int64_t r = (int64_t) blockIdx.x * (ILU0_LEVEL_THREADS / a.G) + team;
+  if (r >= a.m)
+    return;
+  const int slot = team * a.G * ILU0_LDS_PER_LANE;
+  ilu0_sweep_row<T>(a, (int) r, (int) threadIdx.x % a.G, s_cols + slot, s_vals + slot);
+}
+
 // Resets the status word in front of a factor's launches.  A kernel, not hipMemsetAsync.  Observed, cause not established: with
 // a 16-byte hipMemsetAsync here, a graph that recorded the factor and both solves read back arbitrary bits from the word after
 // replay (factors and x exact; the same calls outside a capture were fine).  With this kernel the word replays correctly.
@@ -251,6 +369,35 @@ static int ilu0_factor_typed(spblas_gfx950_handle_t h, spblas_gfx950_ilu0_s* pl,
     } else {
       hipLaunchKernelGGL((ilu0_chain_kernel<T>), dim3(1), dim3(ILU0_CHAIN_THREADS), 0, s, g.l0, g.l1, lv->level_ptr, a);
     }
+  }
+  SPB_HIP(hipGetLastError());
+  return SPBLAS_GFX950_STATUS_SUCCESS;
+}
+
+template <typename T>
+static int ilu0_sweeps_typed(spblas_gfx950_handle_t h, spblas_gfx950_ilu0_s* pl, int sweeps, const int32_t* rowptr,
+                             const int32_t* colind, const T* a_values, T* lu_values, T* work) {
+  hipStream_t s = h->stream;
+  const spblas_gfx950_trsv_s* lv = pl->levels;
+  // a row of level l is final from sweep l on: more than levels - 1 sweeps change nothing
+  const int levels = lv->h_level_ptr.empty() ? 0 : (int) lv->h_level_ptr.size() - 1;
+  const int s_eff = std::min(sweeps, std::max(1, levels - 1));
+  hipLaunchKernelGGL(ilu0_reset_kernel, dim3(1), dim3(64), 0, s, pl->status);
+  ilu0_sweep_args<T> a;
+  a.rowptr = rowptr;
+  a.colind = colind;
+  a.diag = pl->diag;
+  a.a = a_values;
+  a.status = pl->status;
+  a.m = (int) pl->m;
+  a.G = lv->lanes;
+  const unsigned grid = (unsigned) cdiv(pl->m, ILU0_LEVEL_THREADS / a.G);
+  for (int k = 1; k <= s_eff; ++k) {
+    const bool to_work = ((s_eff - k) & 1) != 0;  // the last sweep lands in lu_values
+    a.next = to_work ? work : lu_values;
+    a.prev = k == 1 ? a_values : (to_work ? lu_values : work);  // LU(0) is A itself: no copy
+    a.last = k == s_eff;
+    hipLaunchKernelGGL((ilu0_sweep_kernel<T>), dim3(grid), dim3(ILU0_LEVEL_THREADS), 0, s, a);
   }
   SPB_HIP(hipGetLastError());
   return SPBLAS_GFX950_STATUS_SUCCESS;
@@ -374,6 +521,33 @@ int spblas_gfx950_ilu0_factor(spblas_gfx950_handle_t handle, spblas_gfx950_ilu0_
                                     static_cast<float*>(lu_values));
   return ilu0_factor_typed<double>(handle, plan, rowptr, colind, static_cast<const double*>(a_values),
                                    static_cast<double*>(lu_values));
+}
+
+int spblas_gfx950_ilu0_sweeps(spblas_gfx950_handle_t handle, spblas_gfx950_ilu0_t plan, int64_t m, int64_t nnz, int sweeps,
+                              const int32_t* rowptr, const int32_t* colind, const void* a_values, void* lu_values, void* work,
+                              int value_type) {
+  if (is_complex_type(value_type) || is_lowp_type(value_type))  // complex / 16-bit values: SpMV / SpMM only
+    return SPBLAS_GFX950_STATUS_NOT_SUPPORTED;
+  if (!handle)
+    return SPBLAS_GFX950_STATUS_INVALID_HANDLE;
+  if (!plan || !rowptr || (nnz > 0 && (!colind || !a_values || !lu_values || (!work && sweeps >= 2))))
+    return SPBLAS_GFX950_STATUS_INVALID_POINTER;
+  if (m != plan->m || nnz != plan->nnz || rowptr != plan->rowptr || (nnz > 0 && colind != plan->colind))
+    return SPBLAS_GFX950_STATUS_PLAN_MISMATCH;
+  if (value_type != SPBLAS_GFX950_F32 && value_type != SPBLAS_GFX950_F64)
+    return SPBLAS_GFX950_STATUS_INVALID_VALUE;
+  if (sweeps < 1)
+    return SPBLAS_GFX950_STATUS_INVALID_VALUE;
+  // every sweep re-reads A while the iterates alternate between lu_values and work: no in-place form
+  if (nnz > 0 && (a_values == lu_values || (work && (work == a_values || work == lu_values))))
+    return SPBLAS_GFX950_STATUS_INVALID_VALUE;
+  if (m == 0)
+    return SPBLAS_GFX950_STATUS_SUCCESS;
+  if (value_type == SPBLAS_GFX950_F32)
+    return ilu0_sweeps_typed<float>(handle, plan, sweeps, rowptr, colind, static_cast<const float*>(a_values),
+                                    static_cast<float*>(lu_values), static_cast<float*>(work));
+  return ilu0_sweeps_typed<double>(handle, plan, sweeps, rowptr, colind, static_cast<const double*>(a_values),
+                                   static_cast<double*>(lu_values), static_cast<double*>(work));
 }
 
 } // extern "C"
