@@ -55,6 +55,8 @@ typedef struct spblas_gfx950_plan_s* spblas_gfx950_plan_t;
 typedef struct spblas_gfx950_spgemm_s* spblas_gfx950_spgemm_t;
 typedef struct spblas_gfx950_trsv_s* spblas_gfx950_trsv_t;
 typedef struct spblas_gfx950_ilu0_s* spblas_gfx950_ilu0_t;
+typedef struct spblas_gfx950_multicolor_s* spblas_gfx950_multicolor_t;
+typedef struct spblas_gfx950_permute_s* spblas_gfx950_permute_t;
 
 typedef enum spblas_gfx950_status {
   SPBLAS_GFX950_STATUS_SUCCESS = 0,
@@ -76,7 +78,7 @@ typedef enum spblas_gfx950_datatype {
    * SpMV (op N) and SpMM on CSR with int32 columns only: spmv_plan_create (AUTO / VECTOR / ROWBLOCK; SLICED returns
    * STATUS_NOT_SUPPORTED), spblas_gfx950_spmv[_conj], spblas_gfx950_spmm[_strided[_conj]].  The other entry points that take a
    * value type (spgemm_numeric[_addend], csr_add_numeric, csr_transpose, scale, sptrsv_solve, sptrsm_solve, sptrsv_sweeps,
-   * ilu0_factor, ilu0_sweeps) return STATUS_NOT_SUPPORTED for them, before any other check; so do plan_update_values / plan_detach and the
+   * ilu0_factor, ilu0_sweeps, csr_permute_values, permute_vector) return STATUS_NOT_SUPPORTED for them, before any other check; so do plan_update_values / plan_detach and the
    * two-stage / multi-GPU calls on a complex plan. */
   SPBLAS_GFX950_C32 = 2, /* std::complex<float>  */
   SPBLAS_GFX950_C64 = 3, /* std::complex<double> */
@@ -85,7 +87,8 @@ typedef enum spblas_gfx950_datatype {
    * and SpMM on CSR with int32 columns only: spmv_plan_create (AUTO / VECTOR / ROWBLOCK; AUTO never picks SLICED, SLICED
    * returns STATUS_NOT_SUPPORTED), spblas_gfx950_spmv, spblas_gfx950_spmm[_strided], spmm_inspect.  op = T, the _conj entry
    * points and every other entry point that takes a value type (spgemm_numeric[_addend], csr_add_numeric, csr_transpose,
-   * scale, sptrsv_solve, sptrsm_solve, sptrsv_sweeps, ilu0_factor, ilu0_sweeps) return STATUS_NOT_SUPPORTED for them,
+   * scale, sptrsv_solve, sptrsm_solve, sptrsv_sweeps, ilu0_factor, ilu0_sweeps, csr_permute_values, permute_vector) return
+   * STATUS_NOT_SUPPORTED for them,
    * before any other check; so do plan_update_values / plan_detach / spmv_expand / spmv_reduce_rows on a 16-bit plan. */
   SPBLAS_GFX950_F16 = 4, /* IEEE binary16 (torch.float16) */
   SPBLAS_GFX950_BF16 = 5 /* bfloat16 (torch.bfloat16)     */
@@ -631,6 +634,58 @@ int spblas_gfx950_ilu0_factor(spblas_gfx950_handle_t handle, spblas_gfx950_ilu0_
 int spblas_gfx950_ilu0_sweeps(spblas_gfx950_handle_t handle, spblas_gfx950_ilu0_t plan, int64_t m, int64_t nnz, int sweeps,
                               const int32_t* rowptr, const int32_t* colind, const void* a_values, void* lu_values, void* work,
                               int value_type);
+
+/* ---- multicolour ordering and symmetric permutation  (CSR, int32 indices; no reference counterpart) -------------- */
+/* The exact ilu0_factor and the exact triangular solves pay one hand-off per level of the dependency graph.  Ordering the rows
+ * by the colours of a distance-1 colouring of the graph of A + A^T makes that graph shallow: rows of one colour share no stored
+ * off-diagonal entry, so in B = P A P^T row i depends only on rows of lower colours and BOTH triangles of B have at most
+ * `colours` levels.  The ordering changes the incomplete factor: a Krylov iteration preconditioned with ILU(0) of B usually needs
+ * more iterations than with ILU(0) of A in its natural order -- depth is traded for convergence.
+ *   colouring     Jones-Plassmann with fixed priorities.  key(v) = (uint64(h(v)) << 32) | v, compared unsigned, with
+ *                 h(v) = mix(uint32(v + 1) * 0x9E3779B1u) and mix(x): x ^= x >> 16; x *= 0x85EBCA6Bu; x ^= x >> 13;
+ *                 x *= 0xC2B2AE35u; x ^= x >> 16 (32-bit wraparound).  The neighbours of v are the columns of row v of A and of
+ *                 row v of A^T without v itself (the pattern need not be symmetric; self loops and duplicate entries are legal
+ *                 and ignored).  One launch per round: an uncoloured vertex with an uncoloured neighbour of larger key waits,
+ *                 every other one takes the smallest colour no neighbour holds.
+ *   determinism   the result equals sequential greedy colouring in descending key order whatever the schedule: the colours
+ *                 depend on the pattern alone.  Only the number of rounds may vary from call to call.
+ *   multicolor_create   the inspect: checks the structure on the device (a column outside [0, m) or offsets that do not describe
+ *                 nnz entries: STATUS_INVALID_VALUE), forms the pattern of A^T with spblas_gfx950_csr_transpose, runs the
+ *                 rounds -- the host reads the count of coloured vertices after each, at most m of them -- and sorts the
+ *                 vertices by (colour, index).  It synchronises the handle's stream (STATUS_NOT_SUPPORTED inside a capture)
+ *                 and keeps 3 m + colours + 1 int32 on the device until multicolor_destroy.  A is square, m x m.
+ *   multicolor_info     info[0] colours, [1] rounds, [2] vertices of the largest colour class, [3] lanes per row.
+ *   multicolor_copy     copies the results into caller-allocated int32 device arrays on the stream; any of them may be NULL.
+ *                 perm[m]: new -> old, sorted by (colour, old index); inv_perm[m]: old -> new; color[m];
+ *                 color_ptr[colours + 1]: rows color_ptr[c] .. color_ptr[c + 1] - 1 of the new order have colour c. */
+int spblas_gfx950_multicolor_create(spblas_gfx950_handle_t handle, spblas_gfx950_multicolor_t* plan, int64_t m, int64_t nnz,
+                                    const int32_t* rowptr, const int32_t* colind);
+int spblas_gfx950_multicolor_destroy(spblas_gfx950_handle_t handle, spblas_gfx950_multicolor_t plan);
+int spblas_gfx950_multicolor_info(spblas_gfx950_multicolor_t plan, int64_t info[4]);
+int spblas_gfx950_multicolor_copy(spblas_gfx950_handle_t handle, spblas_gfx950_multicolor_t plan, int32_t* perm,
+                                  int32_t* inv_perm, int32_t* color, int32_t* color_ptr);
+/* B = P A P^T for a square CSR matrix: row i of B is row perm[i] of A with column c renamed inv_perm[c]; the columns of every
+ * row of B are ASCENDING and equal columns keep their source order -- the form ilu0_create / sptrsv_create take.
+ *   csr_permute_create   the inspect: checks on the device that perm is a permutation of 0 .. m - 1 and that rowptr / colind
+ *                 describe an m x m matrix of nnz entries (else STATUS_INVALID_VALUE, with nothing written to B), writes
+ *                 b_rowptr[m + 1] and b_colind[nnz] (caller-allocated, not A's own arrays) and keeps map[nnz], the position in
+ *                 A's arrays of every entry of B.  The rows are sorted by two passes of spblas_gfx950_csr_transpose that carry
+ *                 the source position as payload.  It allocates and synchronises (STATUS_NOT_SUPPORTED inside a capture).
+ *   csr_permute_values   b_values[p] = a_values[map[p]]: one gather launch, nothing allocated, nothing synchronised, so it may
+ *                 be recorded in a graph from its first use -- what a refactorisation on a fixed pattern calls.  Order of
+ *                 checks: C32 / C64 / F16 / BF16 return STATUS_NOT_SUPPORTED before anything else; then handle, pointers,
+ *                 plan against nnz (STATUS_PLAN_MISMATCH), value type (F32 / F64, else STATUS_INVALID_VALUE),
+ *                 a_values == b_values (STATUS_INVALID_VALUE: no in-place form).
+ *   permute_vector       inverse == 0: dst[i] = src[perm[i]] (b into the new order); otherwise dst[perm[i]] = src[i] (x back).
+ *                 n elements, src != dst, F32 / F64; perm is NOT checked (csr_permute_create did).  One launch, capturable. */
+int spblas_gfx950_csr_permute_create(spblas_gfx950_handle_t handle, spblas_gfx950_permute_t* plan, int64_t m, int64_t nnz,
+                                     const int32_t* rowptr, const int32_t* colind, const int32_t* perm, int32_t* b_rowptr,
+                                     int32_t* b_colind);
+int spblas_gfx950_csr_permute_destroy(spblas_gfx950_handle_t handle, spblas_gfx950_permute_t plan);
+int spblas_gfx950_csr_permute_values(spblas_gfx950_handle_t handle, spblas_gfx950_permute_t plan, int64_t nnz,
+                                     const void* a_values, void* b_values, int value_type);
+int spblas_gfx950_permute_vector(spblas_gfx950_handle_t handle, int64_t n, const int32_t* perm, const void* src, void* dst,
+                                 int value_type, int inverse);
 
 /* ---- scale:  values[i] *= alpha  (algorithms/scale_impl.hpp:13-19) --------------------------- */
 /* In-place scaling of a matrix's value array or of a dense vector (n elements, device memory).  A SLICED

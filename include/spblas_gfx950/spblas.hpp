@@ -1049,4 +1049,120 @@ inline std::int64_t ilu0_status(operation_info_t& info) {
 }
 } // namespace gfx950
 
+// ---- multicolour ordering and symmetric permutation (spblas_gfx950_multicolor_* / csr_permute_* / permute_vector; no reference
+// counterpart, hence spblas::gfx950) -----------------------------------------------------------------------------------------
+// multicolor_order colours the graph of A + A^T at distance 1 (Jones-Plassmann with fixed priorities: the colours equal
+// sequential greedy colouring in descending key order and depend on the pattern alone) and sorts the rows by colour.
+// permute forms B = P A P^T with ascending columns: both triangles of B have at most `colors` levels for ilu0 / triangular_solve,
+// at the price of a weaker ILU(0) preconditioner than in the natural order.  A is a square plain csr_view (float / double,
+// int32 indices and offsets); perm, the result arrays and B's arrays are caller-allocated device memory.
+namespace gfx950 {
+struct multicolor_info_t {
+  std::int64_t colors = 0, rounds = 0, max_color_size = 0, lanes_per_row = 0;
+};
+} // namespace gfx950
+
+namespace __gfx950 {
+template <typename State>
+State& state_of(operation_info_t& info) {
+  auto* s = dynamic_cast<State*>(info.state_.get());
+  if (!s) {
+    info.state_ = std::make_unique<State>();
+    s = static_cast<State*>(info.state_.get());
+  }
+  return *s;
+}
+template <typename T>
+permute_state_t& permute_prepare(operation_info_t& info, const csr_view<T, std::int32_t, std::int32_t>& a,
+                                 std::span<const std::int32_t> perm, const csr_view<T, std::int32_t, std::int32_t>& b) {
+  static_assert(std::is_same_v<T, float> || std::is_same_v<T, double>, "permute: float / double values only");
+  if (a.shape()[0] != a.shape()[1] || b.shape()[0] != a.shape()[0] || b.shape()[1] != a.shape()[1] ||
+      perm.size() != static_cast<std::size_t>(a.shape()[0])) {
+    throw std::invalid_argument("permute: matrix dimensions are incompatible.");
+  }
+  if (b.rowptr().size() < static_cast<std::size_t>(a.shape()[0]) + 1 ||
+      (a.size() > 0 && (b.colind().data() == nullptr || b.values().data() == nullptr))) {
+    throw std::invalid_argument("permute: b must hold m + 1 row offsets and A's number of columns and values.");
+  }
+  auto& st = state_of<permute_state_t>(info);
+  if (!st.matches(a.rowptr().data(), a.colind().data(), perm.data(), b.rowptr().data(), b.colind().data(), a.shape()[0],
+                  a.size())) {
+    st.inspect(a.shape()[0], a.size(), a.rowptr().data(), a.colind().data(), perm.data(), b.rowptr().data(),
+               b.colind().data());
+  }
+  return st;
+}
+} // namespace __gfx950
+
+namespace gfx950 {
+// the inspect: synchronises the stream; the results stay in `info` until multicolor_copy fetches them
+template <typename T>
+multicolor_info_t multicolor_order(operation_info_t& info, const csr_view<T, std::int32_t, std::int32_t>& a) {
+  static_assert(std::is_same_v<T, float> || std::is_same_v<T, double>, "multicolor_order: float / double values only");
+  if (a.shape()[0] != a.shape()[1]) {
+    throw std::invalid_argument("multicolor_order: matrix dimensions are incompatible.");
+  }
+  auto& st = __gfx950::state_of<__gfx950::multicolor_state_t>(info);
+  st.inspect(a.shape()[0], a.size(), a.rowptr().data(), a.colind().data());
+  std::int64_t v[4];
+  st.info(v);
+  return multicolor_info_t{v[0], v[1], v[2], v[3]};
+}
+// perm (new -> old, sorted by (colour, old index)), inverse (old -> new), color: m elements; color_ptr: colors + 1.  An empty
+// span is skipped.
+inline void multicolor_copy(operation_info_t& info, std::span<std::int32_t> perm, std::span<std::int32_t> inverse,
+                            std::span<std::int32_t> color, std::span<std::int32_t> color_ptr) {
+  auto& st = __gfx950::state_of<__gfx950::multicolor_state_t>(info);
+  std::int64_t v[4];
+  st.info(v);
+  const auto m = static_cast<std::size_t>(st.rows());
+  if ((!perm.empty() && perm.size() < m) || (!inverse.empty() && inverse.size() < m) || (!color.empty() && color.size() < m) ||
+      (!color_ptr.empty() && color_ptr.size() < static_cast<std::size_t>(v[0]) + 1)) {
+    throw std::invalid_argument("multicolor_copy: an output is shorter than the result.");
+  }
+  st.copy(perm.empty() ? nullptr : perm.data(), inverse.empty() ? nullptr : inverse.data(),
+          color.empty() ? nullptr : color.data(), color_ptr.empty() ? nullptr : color_ptr.data());
+}
+// writes B's row offsets and columns and keeps the source position of every entry (inspect-class: synchronises)
+template <typename T>
+void permute_inspect(operation_info_t& info, const csr_view<T, std::int32_t, std::int32_t>& a,
+                     std::type_identity_t<std::span<const std::int32_t>> perm,
+                     const csr_view<T, std::int32_t, std::int32_t>& b) {
+  __gfx950::permute_prepare(info, a, perm, b);
+  info.update_impl_(a.shape(), a.size());
+}
+template <typename T>
+operation_info_t permute_inspect(const csr_view<T, std::int32_t, std::int32_t>& a,
+                                 std::type_identity_t<std::span<const std::int32_t>> perm,
+                                 const csr_view<T, std::int32_t, std::int32_t>& b) {
+  operation_info_t info;
+  permute_inspect(info, a, perm, b);
+  return info;
+}
+// with the info of permute_inspect for these arrays: only the value gather (one launch, capturable); otherwise inspects first
+template <typename T>
+void permute(operation_info_t& info, const csr_view<T, std::int32_t, std::int32_t>& a,
+             std::type_identity_t<std::span<const std::int32_t>> perm, const csr_view<T, std::int32_t, std::int32_t>& b) {
+  auto& st = __gfx950::permute_prepare(info, a, perm, b);
+  st.template values<T>(a.values().data(), b.values().data());
+}
+template <typename T>
+void permute(const csr_view<T, std::int32_t, std::int32_t>& a, std::type_identity_t<std::span<const std::int32_t>> perm,
+             const csr_view<T, std::int32_t, std::int32_t>& b) {
+  operation_info_t info;
+  permute(info, a, perm, b);
+}
+// inverse == false: dst[i] = src[perm[i]] (b into the new order); true: dst[perm[i]] = src[i] (x back).  src != dst.
+template <typename T>
+void permute_vector(std::span<const std::int32_t> perm, std::type_identity_t<std::span<const T>> src, std::span<T> dst,
+                    bool inverse = false) {
+  static_assert(std::is_same_v<T, float> || std::is_same_v<T, double>, "permute_vector: float / double values only");
+  if (src.size() != perm.size() || dst.size() != perm.size()) {
+    throw std::invalid_argument("permute_vector: perm, src and dst must have one length.");
+  }
+  __gfx950::handle_t h;
+  __gfx950::permute_vector_values<T>(h, static_cast<std::int64_t>(perm.size()), perm.data(), src.data(), dst.data(), inverse);
+}
+} // namespace gfx950
+
 } // namespace spblas

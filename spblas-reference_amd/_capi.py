@@ -129,6 +129,15 @@ PROTOTYPES = [
     ("spblas_gfx950_ilu0_factor", c_int, [c_void_p, c_void_p, c_i64, c_i64, c_void_p, c_void_p, c_void_p, c_void_p, c_int]),
     ("spblas_gfx950_ilu0_sweeps", c_int,
      [c_void_p, c_void_p, c_i64, c_i64, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int]),
+    ("spblas_gfx950_multicolor_create", c_int, [c_void_p, ctypes.POINTER(c_void_p), c_i64, c_i64, c_void_p, c_void_p]),
+    ("spblas_gfx950_multicolor_destroy", c_int, [c_void_p, c_void_p]),
+    ("spblas_gfx950_multicolor_info", c_int, [c_void_p, ctypes.POINTER(c_i64)]),
+    ("spblas_gfx950_multicolor_copy", c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    ("spblas_gfx950_csr_permute_create", c_int,
+     [c_void_p, ctypes.POINTER(c_void_p), c_i64, c_i64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    ("spblas_gfx950_csr_permute_destroy", c_int, [c_void_p, c_void_p]),
+    ("spblas_gfx950_csr_permute_values", c_int, [c_void_p, c_void_p, c_i64, c_void_p, c_void_p, c_int]),
+    ("spblas_gfx950_permute_vector", c_int, [c_void_p, c_i64, c_void_p, c_void_p, c_void_p, c_int, c_int]),
     ("spblas_gfx950_spgemm_set_addend", c_int, [c_void_p, c_void_p, c_i64, c_void_p, c_void_p]),
     ("spblas_gfx950_spgemm_numeric_addend", c_int,
      [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,

@@ -30,13 +30,14 @@ matrix_opt).  Complex operands may be conjugated -- conjugated(A), conjugated(x 
 (t.conj(): the bit is folded into the kernel's flag, nothing is copied) -- and scaled by complex factors: a factor counts
 conjugated iff an odd number of conjugated views wrap it (conjugated(scaled(s, A)) = conj(s) conj(A)).  Everything else with
 complex values -- csc_view / transposed() operands, int64 column indices, SpGEMM, add, transpose, scale, triangular_solve,
-triangular_solve_sweeps, ilu0, ilu0_sweeps -- raises TypeError; an output with the conj bit set raises ValueError.
+triangular_solve_sweeps, ilu0, ilu0_sweeps, multicolor_order, permute, permute_vector -- raises TypeError; an output with the conj bit set raises ValueError.
 
 16-bit values: float16 / bfloat16 for SpMV and SpMM on a csr_view with int32 column indices (int32 / int64 row offsets),
 plan-free or inspected (VECTOR / ROWBLOCK / AUTO plans, matrix_opt), scaled() by real factors.  A, x / B and y / C share the
 one 16-bit type; products and sums are formed in fp32 and every output element is rounded once.  Everything else with 16-bit
 values -- csc_view / transposed() operands, int64 column indices, mixed value types, a complex scaled() factor, conjugated
-views, SpGEMM, add, transpose, scale, triangular_solve, triangular_solve_sweeps, ilu0, ilu0_sweeps, the multi-GPU classes -- raises
+views, SpGEMM, add, transpose, scale, triangular_solve, triangular_solve_sweeps, ilu0, ilu0_sweeps, multicolor_order,
+permute, permute_vector, the multi-GPU classes -- raises
 TypeError (conjugated views: RuntimeError, as for real operands).
 """
 import ctypes
@@ -1856,3 +1857,177 @@ def ilu0_status(info):
     if not isinstance(plan, _Ilu0Plan):
         raise TypeError("ilu0_status: expected the operation_info_t of ilu0_inspect / ilu0")
     return plan.status()
+
+
+# ---- multicolour ordering and symmetric permutation (spblas_gfx950_multicolor_* / csr_permute_* / permute_vector) ----
+class multicolor_order_t:
+    """Result of multicolor_order: int32 device tensors `perm` (new -> old, sorted by (colour, old index)), `inverse`
+    (old -> new), `color` (per row of A) and `color_ptr` (colours + 1 offsets into the new order), plus info()."""
+
+    def __init__(self, perm, inverse, color, color_ptr, info):
+        self.perm, self.inverse, self.color, self.color_ptr, self._info = perm, inverse, color, color_ptr, info
+
+    def info(self):
+        return dict(self._info)
+
+
+def multicolor_order(a):
+    """multicolor_order(a) -> multicolor_order_t: a deterministic distance-1 colouring of the graph of A + A^T (Jones-Plassmann
+    with fixed priorities; the colours equal sequential greedy colouring in descending key order and depend on the pattern
+    alone) and the permutation that sorts the rows by colour.  permute(a, order.perm, b) then gives a matrix whose two triangles
+    have at most info()['colors'] levels for ilu0 / triangular_solve -- at the price of a weaker ILU(0) preconditioner than in
+    the natural order.  `a` is a square plain csr_view (float32 / float64 values, int32 offsets and columns; rows need not be
+    sorted, the pattern need not be symmetric).  Inspect-class: synchronises the stream, refused inside a capture."""
+    a = _ilu0_operand(a, "multicolor_order")
+    dev = a.rowptr().device
+    hd = _Handle.current(dev)
+    m = a.shape()[0]
+    plan = ctypes.c_void_p()
+    st = _capi.lib().spblas_gfx950_multicolor_create(hd.h, ctypes.byref(plan), m, a.size(), _ptr(a.rowptr()), _ptr(a.colind()))
+    if st == _capi.INVALID_VALUE:
+        raise ValueError("multicolor_order: every column must lie inside [0, m) and the row offsets must describe the entries")
+    check(st, "multicolor_order")
+    try:
+        arr = (ctypes.c_int64 * 4)()
+        check(_capi.lib().spblas_gfx950_multicolor_info(plan, arr), "spblas_gfx950_multicolor_info")
+        info = dict(zip(("colors", "rounds", "max_color_size", "lanes_per_row"), list(arr)))
+        perm, inverse, color = (torch.empty(m, dtype=torch.int32, device=dev) for _ in range(3))
+        color_ptr = torch.empty(info["colors"] + 1, dtype=torch.int32, device=dev)
+        check(_capi.lib().spblas_gfx950_multicolor_copy(hd.h, plan, _ptr(perm), _ptr(inverse), _ptr(color), _ptr(color_ptr)),
+              "spblas_gfx950_multicolor_copy")
+    finally:
+        _capi.lib().spblas_gfx950_multicolor_destroy(hd.h, plan)
+    return multicolor_order_t(perm, inverse, color, color_ptr, info)
+
+
+class _PermutePlan:
+    """permute_inspect state: the source position of every entry of B (spblas_gfx950_csr_permute_create)."""
+
+    def __init__(self, hd, plan, key, tensors):
+        self.hd, self.plan, self.key, self.tensors = hd, plan, key, tensors
+
+    def __del__(self):
+        try:
+            if self.plan:
+                _capi.lib().spblas_gfx950_csr_permute_destroy(self.hd.h, self.plan)
+                self.plan = None
+        except Exception:
+            pass
+
+
+def _permute_operands(a, perm, b, what):
+    a = _ilu0_operand(a, what)
+    m, nnz = a.shape()[0], a.size()
+    dev = a.rowptr().device
+    if not _is_tensor(perm) or perm.dtype != torch.int32:
+        raise TypeError(f"{what}: perm must be an int32 tensor")
+    if perm.device != dev or not perm.is_contiguous() or perm.dim() != 1 or perm.numel() != m:
+        raise ValueError(f"{what}: perm must be a contiguous vector of A's {m} rows on A's device")
+    if not isinstance(b, csr_view):
+        raise TypeError(f"{what}: b must be a plain csr_view over caller-allocated arrays, got {type(b).__name__}")
+    bv, br, bc = b.values(), b.rowptr(), b.colind()
+    if not _is_tensor(bv) or not _is_tensor(br) or not _is_tensor(bc):
+        raise TypeError(f"{what}: b's values, row offsets and columns must be tensors")
+    if br.dtype != torch.int32 or bc.dtype != torch.int32:
+        raise TypeError(f"{what}: b must have int32 row offsets and columns, got {br.dtype} / {bc.dtype}")
+    if bv.dtype != a.values().dtype:
+        raise TypeError(f"{what}: b's values must have A's value type {a.values().dtype}, got {bv.dtype}")
+    if any(t.device != dev or not t.is_contiguous() for t in (bv, br, bc)):
+        raise ValueError(f"{what}: b's arrays must be contiguous and live on A's device")
+    if tuple(b.shape()) != tuple(a.shape()):
+        raise ValueError(f"{what}: matrix dimensions are incompatible (b must have A's shape).")
+    if br.numel() < m + 1 or bc.numel() < nnz or bv.numel() < nnz:
+        raise ValueError(f"{what}: b's arrays must hold {m + 1} row offsets and {nnz} columns and values")
+    if br.data_ptr() == a.rowptr().data_ptr() or (nnz > 0 and (bc.data_ptr() == a.colind().data_ptr() or
+                                                               bv.data_ptr() == a.values().data_ptr())):
+        raise ValueError(f"{what}: b must have arrays of its own (there is no in-place form)")
+    return a
+
+
+def _permute_key(a, perm, b):
+    return (a.rowptr().data_ptr(), a.colind().data_ptr(), tuple(a.shape()), a.size(), perm.data_ptr(),
+            b.rowptr().data_ptr(), b.colind().data_ptr())
+
+
+def _permute_plan(a, perm, b):
+    hd = _Handle.current(a.rowptr().device)
+    plan = ctypes.c_void_p()
+    st = _capi.lib().spblas_gfx950_csr_permute_create(hd.h, ctypes.byref(plan), a.shape()[0], a.size(), _ptr(a.rowptr()),
+                                                      _ptr(a.colind()), _ptr(perm), _ptr(b.rowptr()), _ptr(b.colind()))
+    if st == _capi.INVALID_VALUE:
+        raise ValueError("permute_inspect: perm must be a permutation of 0 .. m - 1, every column of A must lie inside [0, m) "
+                         "and A's row offsets must describe its entries")
+    check(st, "permute_inspect")
+    _note_write(b.colind())
+    b.update(b.values(), b.rowptr(), b.colind(), a.shape(), a.size())
+    return _PermutePlan(hd, plan, _permute_key(a, perm, b), (a.rowptr(), a.colind(), perm, b.rowptr(), b.colind()))
+
+
+def permute_inspect(*args):
+    """permute_inspect(a, perm, b) -> operation_info_t, or permute_inspect(info, a, perm, b): checks that `perm` (int32, new -> old)
+    is a permutation (ValueError otherwise, with b untouched), writes the structure of B = P A P^T -- row i of B is row perm[i] of
+    A with column c renamed to the new index of c, columns ascending, equal columns in source order -- into b's row offsets and
+    columns, and keeps the source position of every entry.  `b` is a csr_view over caller-allocated arrays (m + 1 offsets, nnz
+    columns and values) as for transpose.  Inspect-class: allocates, synchronises the stream, refused inside a capture."""
+    if len(args) == 4:
+        info, a, perm, b = args
+        ret = False
+    elif len(args) == 3:
+        a, perm, b = args
+        info, ret = operation_info_t(), True
+    else:
+        raise TypeError("expected (a, perm, b) or (info, a, perm, b)")
+    a = _permute_operands(a, perm, b, "permute_inspect")
+    info.state_ = _permute_plan(a, perm, b)
+    info.update_impl_(a.shape(), a.size())
+    return info if ret else None
+
+
+def permute(*args):
+    """permute(a, perm, b) / permute(info, a, perm, b): B = P A P^T.  Without `info` the call inspects (permute_inspect) and fills
+    b's values.  With the info of permute_inspect for these arrays it only gathers the values, b.values[p] = a.values[source of
+    p]: one launch, nothing allocated or synchronised, so it can be recorded in a graph -- the refresh after A's values changed
+    on a fixed pattern.  An info that was made for other arrays is replaced by a new inspect."""
+    if len(args) == 4:
+        info, a, perm, b = args
+    elif len(args) == 3:
+        a, perm, b = args
+        info = None
+    else:
+        raise TypeError("expected (a, perm, b) or (info, a, perm, b)")
+    a = _permute_operands(a, perm, b, "permute")
+    plan = info.state_ if info is not None and isinstance(info.state_, _PermutePlan) else None
+    if plan is None or plan.key != _permute_key(a, perm, b):
+        plan = _permute_plan(a, perm, b)  # no usable inspect result: analyse now
+        if info is not None:
+            info.state_ = plan
+            info.update_impl_(a.shape(), a.size())
+    hd = _Handle.current(a.rowptr().device)
+    vt, _ = _vtype(a.values(), "permute")
+    check(_capi.lib().spblas_gfx950_csr_permute_values(hd.h, plan.plan, a.size(), _ptr(a.values()), _ptr(b.values()), vt),
+          "permute")
+    _note_write(b.values())
+
+
+def permute_vector(perm, src, dst, inverse=False):
+    """permute_vector(perm, src, dst): dst[i] = src[perm[i]] -- b into the order of permute(a, perm, .); with inverse=True
+    dst[perm[i]] = src[i] -- x back into A's order.  float32 / float64 vectors of perm's length, src and dst different buffers;
+    perm is not checked here (permute_inspect does).  One launch, capturable."""
+    if not _is_tensor(perm) or perm.dtype != torch.int32:
+        raise TypeError("permute_vector: perm must be an int32 tensor")
+    if not _is_tensor(src) or not _is_tensor(dst):
+        raise TypeError("permute_vector: src and dst must be tensors")
+    vt, _ = _vtype(src, "permute_vector")
+    if dst.dtype != src.dtype:
+        raise TypeError("permute_vector: src and dst must have one value type")
+    n = perm.numel()
+    if src.dim() != 1 or dst.dim() != 1 or perm.dim() != 1 or src.numel() != n or dst.numel() != n:
+        raise ValueError("permute_vector: perm, src and dst must be vectors of one length")
+    if not (perm.is_contiguous() and src.is_contiguous() and dst.is_contiguous()) or src.device != perm.device or \
+            dst.device != perm.device:
+        raise ValueError("permute_vector: the vectors must be contiguous and live on one device")
+    if n > 0 and src.data_ptr() == dst.data_ptr():
+        raise ValueError("permute_vector: src and dst must be different buffers")
+    hd = _Handle.current(perm.device)
+    check(_capi.lib().spblas_gfx950_permute_vector(hd.h, n, _ptr(perm), _ptr(src), _ptr(dst), vt, 1 if inverse else 0),
+          "permute_vector")

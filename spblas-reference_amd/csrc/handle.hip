@@ -24,6 +24,7 @@ void preload_sptrsv();
 void preload_sptrsm();
 void preload_sptrsv_sweeps();
 void preload_ilu0();
+void preload_multicolor();
 void preload_multigpu();
 } // namespace spb
 
@@ -88,6 +89,7 @@ int spblas_gfx950_create(spblas_gfx950_handle_t* handle, void* stream) {
       spb::preload_sptrsm();
       spb::preload_sptrsv_sweeps();
       spb::preload_ilu0();
+      spb::preload_multicolor();
       spb::preload_multigpu();
     });
   return SPBLAS_GFX950_STATUS_SUCCESS;
