@@ -57,6 +57,7 @@ typedef struct spblas_gfx950_trsv_s* spblas_gfx950_trsv_t;
 typedef struct spblas_gfx950_ilu0_s* spblas_gfx950_ilu0_t;
 typedef struct spblas_gfx950_multicolor_s* spblas_gfx950_multicolor_t;
 typedef struct spblas_gfx950_permute_s* spblas_gfx950_permute_t;
+typedef struct spblas_gfx950_gs_s* spblas_gfx950_gs_t;
 
 typedef enum spblas_gfx950_status {
   SPBLAS_GFX950_STATUS_SUCCESS = 0,
@@ -78,7 +79,7 @@ typedef enum spblas_gfx950_datatype {
    * SpMV (op N) and SpMM on CSR with int32 columns only: spmv_plan_create (AUTO / VECTOR / ROWBLOCK; SLICED returns
    * STATUS_NOT_SUPPORTED), spblas_gfx950_spmv[_conj], spblas_gfx950_spmm[_strided[_conj]].  The other entry points that take a
    * value type (spgemm_numeric[_addend], csr_add_numeric, csr_transpose, scale, sptrsv_solve, sptrsm_solve, sptrsv_sweeps,
-   * ilu0_factor, ilu0_sweeps, csr_permute_values, permute_vector) return STATUS_NOT_SUPPORTED for them, before any other check; so do plan_update_values / plan_detach and the
+   * ilu0_factor, ilu0_sweeps, csr_permute_values, permute_vector, gs_sweep) return STATUS_NOT_SUPPORTED for them, before any other check; so do plan_update_values / plan_detach and the
    * two-stage / multi-GPU calls on a complex plan. */
   SPBLAS_GFX950_C32 = 2, /* std::complex<float>  */
   SPBLAS_GFX950_C64 = 3, /* std::complex<double> */
@@ -87,7 +88,7 @@ typedef enum spblas_gfx950_datatype {
    * and SpMM on CSR with int32 columns only: spmv_plan_create (AUTO / VECTOR / ROWBLOCK; AUTO never picks SLICED, SLICED
    * returns STATUS_NOT_SUPPORTED), spblas_gfx950_spmv, spblas_gfx950_spmm[_strided], spmm_inspect.  op = T, the _conj entry
    * points and every other entry point that takes a value type (spgemm_numeric[_addend], csr_add_numeric, csr_transpose,
-   * scale, sptrsv_solve, sptrsm_solve, sptrsv_sweeps, ilu0_factor, ilu0_sweeps, csr_permute_values, permute_vector) return
+   * scale, sptrsv_solve, sptrsm_solve, sptrsv_sweeps, ilu0_factor, ilu0_sweeps, csr_permute_values, permute_vector, gs_sweep) return
    * STATUS_NOT_SUPPORTED for them,
    * before any other check; so do plan_update_values / plan_detach / spmv_expand / spmv_reduce_rows on a 16-bit plan. */
   SPBLAS_GFX950_F16 = 4, /* IEEE binary16 (torch.float16) */
@@ -686,6 +687,57 @@ int spblas_gfx950_csr_permute_values(spblas_gfx950_handle_t handle, spblas_gfx95
                                      const void* a_values, void* b_values, int value_type);
 int spblas_gfx950_permute_vector(spblas_gfx950_handle_t handle, int64_t n, const int32_t* perm, const void* src, void* dst,
                                  int value_type, int inverse);
+
+/* ---- multicolour Gauss-Seidel / SOR / SSOR sweeps  (CSR, int32 indices; no reference counterpart) ----------------- */
+/* The smoother the colouring above is made for, and a preconditioner without a factorisation: one symmetric sweep from x = 0
+ * is SSOR -- no ilu0, no level plans, no pivots that can break down, nothing to refresh when the values change.
+ *   order         sigma(i) = perm[i] when gs_create was given a perm, else sigma(i) = i.  Colour c is the positions
+ *                 color_ptr[c] .. color_ptr[c + 1] - 1 of that order (multicolor_copy's color_ptr: with its perm on A itself,
+ *                 without a perm on B = P A P^T).
+ *   row update    dot = sum of a_rc * x_c over the stored entries of row r with c != r, as stored (repeated off-diagonal
+ *                 entries are summed);  g = (b_r - dot) / d_r, d_r the row's one stored diagonal entry;
+ *                 x_r = g when omega == 1 (the old x_r is NOT read), else x_r = fma(omega, g - x_r, x_r).
+ *   sweep         forward: the colours 0 .. C - 1 one after the other, every row of a colour independently; backward:
+ *                 C - 1 .. 0; symmetric: forward, then backward.  `sweeps` repeats that; sweeps == 0 leaves x untouched and
+ *                 launches nothing.  x is updated in place, b is only read, A's values are read as they are at the call and
+ *                 never written.
+ *   determinism   rows of one colour share no stored off-diagonal entry (gs_create checks it), so a launch that updates a
+ *                 colour in place is race free and the sweep equals sequential Gauss-Seidel in colour order bit for bit.  The
+ *                 bits of x depend on the matrix, color_ptr, perm, b, the incoming x, omega, sweeps and the direction -- not on
+ *                 the grid, on earlier calls or on whether the launches were recorded in a graph.  The lanes per row follow
+ *                 sptrsv_create's rule from nnz / m (> 96: 64, > 24: 16, > 6: 8, else 4); a row's entries are reduced in the
+ *                 order of the triangular solve's row kernel, so the bits depend on that lane count alone.
+ *   gs_create     the inspect.  color_ptr[colours + 1] and perm[m] (may be NULL) are int32 device arrays.  It refuses with
+ *                 STATUS_INVALID_VALUE, writing nothing, unless: color_ptr starts at 0, is non-decreasing and ends at m (empty
+ *                 colours are allowed); perm is a permutation of 0 .. m - 1 (the check of csr_permute_create); the row offsets
+ *                 describe nnz entries and every column lies in [0, m); every row has EXACTLY ONE stored diagonal entry; no
+ *                 stored off-diagonal entry (r, c) has r and c in one colour.  color_ptr is checked on the host, where the plan
+ *                 keeps it, everything else on the device.  It allocates and synchronises (STATUS_NOT_SUPPORTED inside a
+ *                 capture).  The plan holds structure only, no values: the colour offsets on the host, the position of every
+ *                 row's diagonal entry (m int32), its own copy of perm (m int32, when one was given) and the lane count.
+ *   gs_info       info[0] colours, [1] rows of the largest colour, [2] lanes per row, [3] launches per forward sweep (the
+ *                 non-empty colours).
+ *   gs_sweep      one launch per non-empty colour and half-sweep on the handle's stream; nothing allocated, nothing
+ *                 synchronised, no pointer kept, so it records into a graph from its first call.  omega points at one host
+ *                 scalar of the value type and is taken as given: convergence is the caller's business.  Order of checks:
+ *                 C32 / C64 / F16 / BF16 return STATUS_NOT_SUPPORTED before anything else; then handle, pointers (the plan
+ *                 included), sizes, values (direction, sweeps < 0, b == x, a value type other than F32 / F64:
+ *                 STATUS_INVALID_VALUE), plan against m and nnz (STATUS_PLAN_MISMATCH).  m == 0 succeeds and launches nothing.
+ * Not offered: a block of right-hand sides, weighted Jacobi, an implied zero initial guess that skips the gathers, several
+ * colours per launch, scaled operands, complex / 16-bit values, int64 indices, CSC operands, distance-2 colourings. */
+typedef enum spblas_gfx950_gs_direction {
+  SPBLAS_GFX950_GS_FORWARD = 0,
+  SPBLAS_GFX950_GS_BACKWARD = 1,
+  SPBLAS_GFX950_GS_SYMMETRIC = 2
+} spblas_gfx950_gs_direction;
+int spblas_gfx950_gs_create(spblas_gfx950_handle_t handle, spblas_gfx950_gs_t* plan, int64_t m, int64_t nnz,
+                            const int32_t* rowptr, const int32_t* colind, int64_t colours, const int32_t* color_ptr,
+                            const int32_t* perm /* may be NULL */);
+int spblas_gfx950_gs_destroy(spblas_gfx950_handle_t handle, spblas_gfx950_gs_t plan);
+int spblas_gfx950_gs_info(spblas_gfx950_gs_t plan, int64_t info[4]);
+int spblas_gfx950_gs_sweep(spblas_gfx950_handle_t handle, spblas_gfx950_gs_t plan, int64_t m, int64_t nnz, int sweeps,
+                           int direction, const void* omega, const int32_t* rowptr, const int32_t* colind, const void* values,
+                           const void* b, void* x, int value_type);
 
 /* ---- scale:  values[i] *= alpha  (algorithms/scale_impl.hpp:13-19) --------------------------- */
 /* In-place scaling of a matrix's value array or of a dense vector (n elements, device memory).  A SLICED

@@ -1165,4 +1165,58 @@ void permute_vector(std::span<const std::int32_t> perm, std::type_identity_t<std
 }
 } // namespace gfx950
 
+// ---- multicolour Gauss-Seidel / SOR / SSOR sweeps (spblas_gfx950_gs_*; no reference counterpart, hence spblas::gfx950) ---------
+// sigma(i) = perm[i] when a perm was given, else i; colour c is the positions color_ptr[c] .. color_ptr[c + 1] - 1.  One row update:
+//   dot = sum of a_rc x_c over the stored entries of row r with c != r (repeated off-diagonal entries are summed)
+//   g = (b_r - dot) / d_r, d_r the row's one stored diagonal entry;  x_r = g when omega == 1 (the old x_r is not read), else
+//   x_r = fma(omega, g - x_r, x_r).
+// forward: colours 0 .. C - 1 one after the other, backward: C - 1 .. 0, symmetric: forward then backward; `sweeps` repeats that
+// (0: x untouched, nothing launched).  x is updated in place, b only read, A's values read as they are at the call.  The result
+// equals sequential Gauss-Seidel in colour order bit for bit and does not depend on the grid, earlier calls or graph capture.
+// gauss_seidel_inspect checks (std::invalid_argument otherwise): color_ptr runs from 0 to m without descending (empty colours
+// allowed); perm is a permutation; the offsets describe the entries, columns in [0, m); exactly one stored diagonal entry per
+// row; no stored off-diagonal entry joins two rows of one colour.  gauss_seidel never inspects by itself: an info that is not a
+// gauss_seidel_inspect of these row offsets and columns throws std::invalid_argument.  One symmetric sweep from x = 0 is SSOR.
+// Not offered: a block of right-hand sides, weighted Jacobi, an implied zero initial guess, several colours per launch, scaled
+// / complex / 16-bit / int64 / csc_view operands, distance-2 colourings.
+namespace gfx950 {
+// color_ptr (colours + 1) and perm (m, or empty) are int32 device arrays.  Inspect-class: allocates and synchronises.
+template <typename T>
+gauss_seidel_info_t gauss_seidel_inspect(operation_info_t& info, const csr_view<T, std::int32_t, std::int32_t>& a,
+                                         std::type_identity_t<std::span<const std::int32_t>> color_ptr,
+                                         std::type_identity_t<std::span<const std::int32_t>> perm = {}) {
+  static_assert(std::is_same_v<T, float> || std::is_same_v<T, double>, "gauss_seidel: float / double values only");
+  if (a.shape()[0] != a.shape()[1] || color_ptr.empty() ||
+      (!perm.empty() && perm.size() != static_cast<std::size_t>(a.shape()[0]))) {
+    throw std::invalid_argument("gauss_seidel_inspect: matrix dimensions are incompatible.");
+  }
+  auto& st = __gfx950::state_of<__gfx950::gs_state_t>(info);
+  st.inspect(a.shape()[0], a.size(), a.rowptr().data(), a.colind().data(), static_cast<std::int64_t>(color_ptr.size()) - 1,
+             color_ptr.data(), perm.empty() ? nullptr : perm.data());
+  info.update_impl_(a.shape(), a.size());
+  std::int64_t v[4];
+  st.info(v);
+  return gauss_seidel_info_t{v[0], v[1], v[2], v[3]};
+}
+// b and x: m elements of A's type in device memory, different buffers.  Capturable from the first call.
+template <typename T>
+void gauss_seidel(operation_info_t& info, const csr_view<T, std::int32_t, std::int32_t>& a,
+                  std::type_identity_t<std::span<const T>> b, std::type_identity_t<std::span<T>> x, int sweeps = 1,
+                  std::type_identity_t<T> omega = T(1), gs_direction direction = gs_direction::forward) {
+  static_assert(std::is_same_v<T, float> || std::is_same_v<T, double>, "gauss_seidel: float / double values only");
+  const auto m = static_cast<std::size_t>(a.shape()[0]);
+  if (a.shape()[0] != a.shape()[1] || b.size() != m || x.size() != m) {
+    throw std::invalid_argument("gauss_seidel: matrix dimensions are incompatible.");
+  }
+  auto* st = dynamic_cast<__gfx950::gs_state_t*>(info.state_.get());
+  if (!st || !st->matches(a.rowptr().data(), a.colind().data(), a.shape()[0], a.size())) {
+    throw std::invalid_argument("gauss_seidel: info must be the result of gauss_seidel_inspect for these row offsets and columns");
+  }
+  if (sweeps < 0 || (m > 0 && b.data() == x.data())) {
+    throw std::invalid_argument("gauss_seidel: sweeps must not be negative and b and x must be different buffers");
+  }
+  st->template sweep<T>(sweeps, static_cast<int>(direction), omega, a.values().data(), b.data(), x.data());
+}
+} // namespace gfx950
+
 } // namespace spblas

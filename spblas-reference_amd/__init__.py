@@ -18,4 +18,4 @@ from .api import (  # noqa: F401
     transposed, triangular_solve, triangular_solve_inspect, triangular_solve_sweeps, upper_triangle_t, lower_triangle_t,
     implicit_unit_diagonal_t, explicit_diagonal_t, upper_triangle, lower_triangle, implicit_unit_diagonal,
     explicit_diagonal, ilu0, ilu0_inspect, ilu0_status, ilu0_sweeps, multicolor_order, multicolor_order_t,
-    permute, permute_inspect, permute_vector)
+    permute, permute_inspect, permute_vector, gauss_seidel, gauss_seidel_inspect)

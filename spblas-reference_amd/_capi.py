@@ -30,6 +30,7 @@ I32, I64 = 0, 1
 OP_N, OP_T = 0, 1
 LOWER, UPPER = 0, 1
 DIAG_EXPLICIT, DIAG_UNIT = 0, 1
+GS_FORWARD, GS_BACKWARD, GS_SYMMETRIC = 0, 1, 2
 SPMV_AUTO, SPMV_VECTOR, SPMV_ROWBLOCK, SPMV_SLICED = 0, 1, 2, 3
 OPT_BIN_ROW_ALIGN = 1
 OPT_MAX_KSPLIT = 2
@@ -138,6 +139,12 @@ PROTOTYPES = [
     ("spblas_gfx950_csr_permute_destroy", c_int, [c_void_p, c_void_p]),
     ("spblas_gfx950_csr_permute_values", c_int, [c_void_p, c_void_p, c_i64, c_void_p, c_void_p, c_int]),
     ("spblas_gfx950_permute_vector", c_int, [c_void_p, c_i64, c_void_p, c_void_p, c_void_p, c_int, c_int]),
+    ("spblas_gfx950_gs_create", c_int,
+     [c_void_p, ctypes.POINTER(c_void_p), c_i64, c_i64, c_void_p, c_void_p, c_i64, c_void_p, c_void_p]),
+    ("spblas_gfx950_gs_destroy", c_int, [c_void_p, c_void_p]),
+    ("spblas_gfx950_gs_info", c_int, [c_void_p, ctypes.POINTER(c_i64)]),
+    ("spblas_gfx950_gs_sweep", c_int,
+     [c_void_p, c_void_p, c_i64, c_i64, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int]),
     ("spblas_gfx950_spgemm_set_addend", c_int, [c_void_p, c_void_p, c_i64, c_void_p, c_void_p]),
     ("spblas_gfx950_spgemm_numeric_addend", c_int,
      [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,

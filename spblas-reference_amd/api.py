@@ -30,14 +30,15 @@ matrix_opt).  Complex operands may be conjugated -- conjugated(A), conjugated(x 
 (t.conj(): the bit is folded into the kernel's flag, nothing is copied) -- and scaled by complex factors: a factor counts
 conjugated iff an odd number of conjugated views wrap it (conjugated(scaled(s, A)) = conj(s) conj(A)).  Everything else with
 complex values -- csc_view / transposed() operands, int64 column indices, SpGEMM, add, transpose, scale, triangular_solve,
-triangular_solve_sweeps, ilu0, ilu0_sweeps, multicolor_order, permute, permute_vector -- raises TypeError; an output with the conj bit set raises ValueError.
+triangular_solve_sweeps, ilu0, ilu0_sweeps, multicolor_order, permute, permute_vector, gauss_seidel -- raises TypeError; an output
+with the conj bit set raises ValueError.
 
 16-bit values: float16 / bfloat16 for SpMV and SpMM on a csr_view with int32 column indices (int32 / int64 row offsets),
 plan-free or inspected (VECTOR / ROWBLOCK / AUTO plans, matrix_opt), scaled() by real factors.  A, x / B and y / C share the
 one 16-bit type; products and sums are formed in fp32 and every output element is rounded once.  Everything else with 16-bit
 values -- csc_view / transposed() operands, int64 column indices, mixed value types, a complex scaled() factor, conjugated
 views, SpGEMM, add, transpose, scale, triangular_solve, triangular_solve_sweeps, ilu0, ilu0_sweeps, multicolor_order,
-permute, permute_vector, the multi-GPU classes -- raises
+permute, permute_vector, gauss_seidel, the multi-GPU classes -- raises
 TypeError (conjugated views: RuntimeError, as for real operands).
 """
 import ctypes
@@ -2031,3 +2032,128 @@ def permute_vector(perm, src, dst, inverse=False):
     hd = _Handle.current(perm.device)
     check(_capi.lib().spblas_gfx950_permute_vector(hd.h, n, _ptr(perm), _ptr(src), _ptr(dst), vt, 1 if inverse else 0),
           "permute_vector")
+
+
+# ---- multicolour Gauss-Seidel / SOR / SSOR sweeps (spblas_gfx950_gs_*; no reference counterpart) ----
+class _GsPlan:
+    """gauss_seidel_inspect state: the colour offsets, the position of every row's diagonal entry and the row order
+    (spblas_gfx950_gs_create).  Structure only, no values."""
+
+    def __init__(self, hd, plan, key, tensors):
+        self.hd, self.plan, self.key, self.tensors = hd, plan, key, tensors
+
+    def info(self):
+        arr = (ctypes.c_int64 * 4)()
+        check(_capi.lib().spblas_gfx950_gs_info(self.plan, arr), "spblas_gfx950_gs_info")
+        return dict(zip(("colors", "max_color_size", "lanes_per_row", "launches_per_forward_sweep"), list(arr)))
+
+    def __del__(self):
+        try:
+            if self.plan:
+                _capi.lib().spblas_gfx950_gs_destroy(self.hd.h, self.plan)
+                self.plan = None
+        except Exception:
+            pass
+
+
+_GS_DIRECTIONS = {"forward": _capi.GS_FORWARD, "backward": _capi.GS_BACKWARD, "symmetric": _capi.GS_SYMMETRIC}
+
+
+def _gs_key(a):
+    return (a.rowptr().data_ptr(), a.colind().data_ptr(), tuple(a.shape()), a.size())
+
+
+def gauss_seidel_inspect(*args, perm=None):
+    """gauss_seidel_inspect(a, color_ptr, perm=None) -> operation_info_t, or gauss_seidel_inspect(info, a, color_ptr, perm=None):
+    the inspect of gauss_seidel.  The row order is sigma(i) = perm[i] when a perm is given, else sigma(i) = i; colour c is the
+    positions color_ptr[c] .. color_ptr[c + 1] - 1 of that order (multicolor_order's color_ptr: with order.perm on A itself,
+    without a perm on the permuted B).  `a` is a square plain csr_view (float32 / float64 values, int32 offsets and columns);
+    color_ptr and perm are contiguous int32 device vectors.  ValueError unless color_ptr starts at 0, is non-decreasing and ends
+    at m (empty colours are allowed), perm is a permutation of 0 .. m - 1, the row offsets describe the entries, every column
+    lies in [0, m), every row has exactly one stored diagonal entry and no stored off-diagonal entry joins two rows of one
+    colour -- the last is what makes the in-place sweep race free, so it is checked and not assumed.  The result holds structure
+    only (no values).  Inspect-class: allocates, synchronises the stream, refused inside a capture."""
+    if len(args) >= 2 and isinstance(args[0], operation_info_t):
+        info, ret, rest = args[0], False, args[1:]
+    else:
+        info, ret, rest = operation_info_t(), True, args
+    if len(rest) == 3 and perm is None:
+        a, color_ptr, perm = rest
+    elif len(rest) == 2:
+        a, color_ptr = rest
+    else:
+        raise TypeError("expected (a, color_ptr, perm=None) or (info, a, color_ptr, perm=None)")
+    what = "gauss_seidel_inspect"
+    a = _ilu0_operand(a, what)
+    m = a.shape()[0]
+    dev = a.rowptr().device
+    if not _is_tensor(color_ptr) or color_ptr.dtype != torch.int32:
+        raise TypeError(f"{what}: color_ptr must be an int32 tensor")
+    if color_ptr.device != dev or not color_ptr.is_contiguous() or color_ptr.dim() != 1 or color_ptr.numel() < 1:
+        raise ValueError(f"{what}: color_ptr must be a contiguous vector of colours + 1 offsets on A's device")
+    if perm is not None:
+        if not _is_tensor(perm) or perm.dtype != torch.int32:
+            raise TypeError(f"{what}: perm must be an int32 tensor or None")
+        if perm.device != dev or not perm.is_contiguous() or perm.dim() != 1 or perm.numel() != m:
+            raise ValueError(f"{what}: perm must be a contiguous vector of A's {m} rows on A's device")
+    hd = _Handle.current(dev)
+    plan = ctypes.c_void_p()
+    st = _capi.lib().spblas_gfx950_gs_create(hd.h, ctypes.byref(plan), m, a.size(), _ptr(a.rowptr()), _ptr(a.colind()),
+                                             color_ptr.numel() - 1, _ptr(color_ptr), _ptr(perm))
+    if st == _capi.INVALID_VALUE:
+        raise ValueError(f"{what}: color_ptr must run from 0 to m without descending, perm must be a permutation of 0 .. m - 1, "
+                         "the row offsets must describe the entries with every column inside [0, m), every row must store "
+                         "exactly one diagonal entry and no off-diagonal entry may join two rows of one colour")
+    check(st, what)
+    info.state_ = _GsPlan(hd, plan, _gs_key(a), (a.rowptr(), a.colind()))
+    info.update_impl_(a.shape(), a.size())
+    return info if ret else None
+
+
+def gauss_seidel(info, a, b, x, sweeps=1, omega=1.0, direction="forward"):
+    """gauss_seidel(info, a, b, x, sweeps=1, omega=1.0, direction="forward"): multicolour Gauss-Seidel / SOR sweeps on A x = b,
+    x updated IN PLACE (spblas_gfx950_gs_sweep; no reference counterpart).  The colouring lives in `info`, the result of
+    gauss_seidel_inspect for these row offsets and columns (anything else: ValueError -- the call never inspects by itself).
+    One row update is  dot = sum of a_rc x_c over the stored entries with c != r;  g = (b_r - dot) / d_r;  x_r = g when
+    omega == 1 (the old x_r is not read), else x_r = fma(omega, g - x_r, x_r).  "forward" updates the colours 0 .. C - 1 one after
+    the other, "backward" C - 1 .. 0, "symmetric" forward then backward; `sweeps` repeats that (0: x untouched, nothing
+    launched).  One symmetric sweep from x = 0 is the SSOR preconditioner.  The result equals sequential Gauss-Seidel in colour
+    order bit for bit and does not depend on the grid, earlier calls or graph capture.  A's values are read as they are at the
+    call (the info holds structure only); b is only read.  One launch per non-empty colour and half-sweep, nothing allocated or
+    synchronised: recordable in a graph from the first call.  `a`: square plain csr_view, float32 / float64, int32 indices; b and
+    x: contiguous vectors of m elements of A's type on A's device in different buffers (scaled(b) is refused); omega is taken as
+    given.  Not offered: a block of right-hand sides, weighted Jacobi, an implied zero initial guess, several colours per
+    launch, scaled / complex / 16-bit / int64 / csc_view operands, distance-2 colourings."""
+    what = "gauss_seidel"
+    a = _ilu0_operand(a, what)
+    m = a.shape()[0]
+    av = a.values()
+    for name, t in (("b", b), ("x", x)):
+        if not _is_tensor(t):
+            raise TypeError(f"{what}: {name} must be a tensor (scaled and other views are not supported), got {type(t).__name__}")
+        if t.dtype != av.dtype:
+            raise TypeError(f"{what}: {name} must have A's value type {av.dtype}, got {t.dtype}")
+        if t.dim() == 2:
+            raise NotImplementedError(f"{what}: vectors only (a block of right-hand sides is not offered)")
+        if t.dim() != 1 or t.numel() != m or not t.is_contiguous() or t.device != av.device:
+            raise ValueError(f"{what}: {name} must be a contiguous vector of A's {m} rows on A's device")
+    if m > 0 and b.data_ptr() == x.data_ptr():
+        raise ValueError(f"{what}: b and x must be different buffers")
+    if isinstance(sweeps, bool) or not isinstance(sweeps, int):
+        raise TypeError(f"{what}: sweeps must be an int")
+    if sweeps < 0 or sweeps > 2 ** 31 - 1:
+        raise ValueError(f"{what}: sweeps must be a non-negative int")
+    if isinstance(omega, bool) or not isinstance(omega, (int, float)):
+        raise TypeError(f"{what}: omega must be a real number")
+    if not isinstance(direction, str) or direction not in _GS_DIRECTIONS:
+        raise ValueError(f"{what}: direction must be 'forward', 'backward' or 'symmetric'")
+    plan = getattr(info, "state_", None)
+    if not isinstance(plan, _GsPlan) or plan.key != _gs_key(a):
+        raise ValueError(f"{what}: info must be the result of gauss_seidel_inspect for these row offsets and columns")
+    hd = _Handle.current(a.rowptr().device)
+    vt, ct = _vtype(av, what)
+    w = ct(omega)
+    check(_capi.lib().spblas_gfx950_gs_sweep(hd.h, plan.plan, m, a.size(), sweeps, _GS_DIRECTIONS[direction], ctypes.byref(w),
+                                             _ptr(a.rowptr()), _ptr(a.colind()), _ptr(av), _ptr(b), _ptr(x), vt), what)
+    if sweeps > 0:
+        _note_write(x)

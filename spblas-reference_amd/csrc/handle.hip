@@ -25,6 +25,7 @@ void preload_sptrsm();
 void preload_sptrsv_sweeps();
 void preload_ilu0();
 void preload_multicolor();
+void preload_gauss_seidel();
 void preload_multigpu();
 } // namespace spb
 
@@ -90,6 +91,7 @@ int spblas_gfx950_create(spblas_gfx950_handle_t* handle, void* stream) {
       spb::preload_sptrsv_sweeps();
       spb::preload_ilu0();
       spb::preload_multicolor();
+      spb::preload_gauss_seidel();
       spb::preload_multigpu();
     });
   return SPBLAS_GFX950_STATUS_SUCCESS;
