@@ -1117,19 +1117,20 @@ def _is_sparse(t):
     return isinstance(get_ultimate_base(t), (csr_view, csc_view))
 
 
-def _split_info(args):
-    if len(args) == 4:
-        return args[0], args[1], args[2], args[3]
-    if len(args) == 3:
-        return None, args[0], args[1], args[2]
-    raise TypeError("expected (a, b, c) or (info, a, b, c)")
+def _leading_info(args, n, names):
+    """args = the n operands `names`, with or without an info in front -> (info or None, the operands)."""
+    if len(args) == n + 1:
+        return args[0], args[1:]
+    if len(args) == n:
+        return None, args
+    raise TypeError(f"expected ({names}) or (info, {names})")
 
 
 def multiply(*args):
     """multiply(a, b, c) / multiply(info, a, b, c): c = a * b.
     SpMV when b is a vector, SpMM when b is a dense matrix
     (vendor/rocsparse/detail/spmv_impl.hpp:25,87; vendor/onemkl_sycl/spmm_impl.hpp:96-125)."""
-    info, a, b, c = _split_info(args)
+    info, (a, b, c) = _leading_info(args, 3, "a, b, c")
     b_base = get_ultimate_base(b)
     if isinstance(info, spgemm_state_t) or _is_sparse(b):
         raise TypeError("SpGEMM is two-phase on device backends: use multiply_compute + multiply_fill")
@@ -1155,7 +1156,7 @@ def multiply_inspect(*args, alg=_capi.SPMV_AUTO, values_will_change=False):
     for that plan explicitly, with the same contract.  values_will_change=True (a time-stepping caller) makes such a plan
     keep the source position of every entry from the start (+4 B per entry): the first refresh is then a gather like every
     later one instead of a second inspect (SPBLAS_GFX950_OPT_VALUE_SNAPSHOT = 2)."""
-    info, a, b, c = _split_info(args)
+    info, (a, b, c) = _leading_info(args, 3, "a, b, c")
     ret = info is None
     if info is None:
         info = operation_info_t()
@@ -1339,7 +1340,7 @@ def multiply_compute(*args):
         if not isinstance(args[0], spgemm_state_t):
             raise TypeError("multiply_compute(state, a, b, c, d): the five-argument form takes a spgemm_state_t")
         return _symbolic(*args)
-    info, a, b, c = _split_info(args)
+    info, (a, b, c) = _leading_info(args, 3, "a, b, c")
     if isinstance(info, spgemm_state_t):
         return _symbolic(info, a, b, c)
     ret = info is None
@@ -1438,7 +1439,7 @@ def _add_numeric(state, a, b, c):
 def add_inspect(*args):
     """add_inspect(a, b, c) -> operation_info_t / add_inspect(info, a, b, c)
     (algorithms/add.hpp:15-19, add_impl.hpp:79-108): structural nnz of A + B; also writes c.rowptr."""
-    info, a, b, c = _split_info(args)
+    info, (a, b, c) = _leading_info(args, 3, "a, b, c")
     ret = info is None
     if info is None:
         info = operation_info_t()
@@ -1485,16 +1486,33 @@ upper_triangle, lower_triangle = upper_triangle_t(), lower_triangle_t()
 implicit_unit_diagonal, explicit_diagonal = implicit_unit_diagonal_t(), explicit_diagonal_t()
 
 
-class _TrsvPlan:
-    """triangular_solve_inspect state: level sets of the dependency graph (spblas_gfx950_sptrsv_create)."""
+class _NativePlan:
+    """The state_ of a solver-side inspect: a plan of the library (destroyed with this object), the key of the arrays it was made
+    for and the tensors it keeps alive.  Subclasses name their C entry points."""
+    _destroy = None
+    _info_call, _info_names = None, ()  # (a plan without an info entry point has no info())
 
-    def __init__(self, hd, plan, key):
-        self.hd, self.plan, self.key = hd, plan, key
+    def __init__(self, hd, plan, key, tensors=None):
+        self.hd, self.plan, self.key, self.tensors = hd, plan, key, tensors
 
     def info(self):
         arr = (ctypes.c_int64 * 4)()
-        check(_capi.lib().spblas_gfx950_sptrsv_info(self.plan, arr), "spblas_gfx950_sptrsv_info")
-        return dict(zip(("levels", "max_level_width", "launches_per_solve", "lanes_per_row"), list(arr)))
+        check(getattr(_capi.lib(), self._info_call)(self.plan, arr), self._info_call)
+        return dict(zip(self._info_names, list(arr)))
+
+    def __del__(self):
+        try:
+            if self.plan:
+                getattr(_capi.lib(), self._destroy)(self.hd.h, self.plan)
+                self.plan = None
+        except Exception:
+            pass
+
+
+class _TrsvPlan(_NativePlan):
+    """triangular_solve_inspect state: level sets of the dependency graph (spblas_gfx950_sptrsv_create)."""
+    _destroy, _info_call = "spblas_gfx950_sptrsv_destroy", "spblas_gfx950_sptrsv_info"
+    _info_names = ("levels", "max_level_width", "launches_per_solve", "lanes_per_row")
 
     def check_status(self):
         """Synchronises the stream; raises if a device-side wait of the last solve gave up (spblas_gfx950_sptrsv_status)."""
@@ -1503,14 +1521,6 @@ class _TrsvPlan:
         check(_capi.lib().spblas_gfx950_sptrsv_status(hd.h, self.plan, ctypes.byref(st)), "spblas_gfx950_sptrsv_status")
         if st.value != 0:
             raise RuntimeError("triangular_solve: a device-side wait ran into its bound; the result is not valid")
-
-    def __del__(self):
-        try:
-            if self.plan:
-                _capi.lib().spblas_gfx950_sptrsv_destroy(self.hd.h, self.plan)
-                self.plan = None
-        except Exception:
-            pass
 
 
 def _trsv_operands(a, uplo, diag, b, x):
@@ -1565,14 +1575,10 @@ def triangular_solve_inspect(*args):
     """triangular_solve_inspect(a, uplo, diag, b, x) -> operation_info_t, or with a leading info
     (algorithms/triangular_solve.hpp:8-15).  The reference's CPU inspect is empty
     (triangular_solve_impl.hpp:13-38); here it builds the level sets the device solve needs."""
-    if len(args) == 6:
-        info, a, uplo, diag, b, x = args
-        ret = False
-    elif len(args) == 5:
-        a, uplo, diag, b, x = args
-        info, ret = operation_info_t(), True
-    else:
-        raise TypeError("expected (a, uplo, diag, b, x) or (info, a, uplo, diag, b, x)")
+    info, (a, uplo, diag, b, x) = _leading_info(args, 5, "a, uplo, diag, b, x")
+    ret = info is None
+    if ret:
+        info = operation_info_t()
     a_base = _trsv_operands(a, uplo, diag, b, x)
     info.state_ = _trsv_plan(a_base, uplo, diag)
     return info if ret else None
@@ -1583,13 +1589,7 @@ def triangular_solve(*args):
     x = inv(A) b using only the named triangle of A (triangular_solve_impl.hpp:41-107).  b and x may both be (m, n) tensors,
     row- or column-major (windows of wider tensors included): X(:, j) = inv(A) B(:, j) for all columns in one solve.  A plan
     made by triangular_solve_inspect with vectors serves matrices and the other way round."""
-    if len(args) == 6:
-        info, a, uplo, diag, b, x = args
-    elif len(args) == 5:
-        a, uplo, diag, b, x = args
-        info = None
-    else:
-        raise TypeError("expected (a, uplo, diag, b, x) or (info, a, uplo, diag, b, x)")
+    info, (a, uplo, diag, b, x) = _leading_info(args, 5, "a, uplo, diag, b, x")
     a_base = _trsv_operands(a, uplo, diag, b, x)
     plan = info.state_ if info is not None and isinstance(info.state_, _TrsvPlan) else None
     if plan is None or plan.key != _trsv_key(a_base, uplo, diag):
@@ -1637,13 +1637,7 @@ def triangular_solve_sweeps(*args):
     this matrix, triangle and diagonal narrows the later sweeps to the rows that can still change; without one every sweep
     covers all rows -- the call never inspects by itself.  The bits of x are the same either way.  A block of right-hand sides
     (2-D b / x) raises NotImplementedError."""
-    if len(args) == 7:
-        info, a, uplo, diag, b, x, sweeps = args
-    elif len(args) == 6:
-        a, uplo, diag, b, x, sweeps = args
-        info = None
-    else:
-        raise TypeError("expected (a, uplo, diag, b, x, sweeps) or (info, a, uplo, diag, b, x, sweeps)")
+    info, (a, uplo, diag, b, x, sweeps) = _leading_info(args, 6, "a, uplo, diag, b, x, sweeps")
     bb = get_ultimate_base(b)
     if (_is_tensor(bb) and bb.dim() == 2) or (_is_tensor(x) and x.dim() == 2):
         raise NotImplementedError("gfx950 triangular_solve_sweeps: vectors only (a block of right-hand sides is not offered)")
@@ -1675,16 +1669,10 @@ def triangular_solve_sweeps(*args):
 
 
 # --------------------------------------------------------------------------- ILU(0) (no reference counterpart)
-class _Ilu0Plan:
+class _Ilu0Plan(_NativePlan):
     """ilu0_inspect state: the lower level plan and the diagonal positions of A's pattern (spblas_gfx950_ilu0_create)."""
-
-    def __init__(self, hd, plan, key, tensors):
-        self.hd, self.plan, self.key, self.tensors = hd, plan, key, tensors
-
-    def info(self):
-        arr = (ctypes.c_int64 * 4)()
-        check(_capi.lib().spblas_gfx950_ilu0_info(self.plan, arr), "spblas_gfx950_ilu0_info")
-        return dict(zip(("levels", "max_level_width", "launches_per_factor", "lanes_per_row"), list(arr)))
+    _destroy, _info_call = "spblas_gfx950_ilu0_destroy", "spblas_gfx950_ilu0_info"
+    _info_names = ("levels", "max_level_width", "launches_per_factor", "lanes_per_row")
 
     def status(self):
         row = ctypes.c_int64(-1)
@@ -1692,17 +1680,10 @@ class _Ilu0Plan:
         check(_capi.lib().spblas_gfx950_ilu0_status(hd.h, self.plan, ctypes.byref(row)), "spblas_gfx950_ilu0_status")
         return int(row.value)
 
-    def __del__(self):
-        try:
-            if self.plan:
-                _capi.lib().spblas_gfx950_ilu0_destroy(self.hd.h, self.plan)
-                self.plan = None
-        except Exception:
-            pass
 
-
-def _ilu0_operand(a, what):
-    """The plain csr_view ILU(0) takes; TypeError for every other operand, dtype or index type."""
+def _square_csr_operand(a, what):
+    """The square plain csr_view ilu0, multicolor_order, permute and gauss_seidel take; TypeError for every other operand, dtype
+    or index type."""
     if not isinstance(a, csr_view):
         raise TypeError(f"{what}: the operand must be a plain csr_view (scaled, conjugated, transposed and csc_view "
                         f"operands are not supported), got {type(a).__name__}")
@@ -1722,8 +1703,18 @@ def _ilu0_operand(a, what):
     return a
 
 
-def _ilu0_key(a):
+def _structure_key(a):
     return (a.rowptr().data_ptr(), a.colind().data_ptr(), tuple(a.shape()), a.size())
+
+
+def _perm_vector(perm, m, dev, what, optional=False):
+    """perm as the inspects take it: a contiguous int32 vector of A's m rows on A's device (or None where it is optional)."""
+    if perm is None and optional:
+        return
+    if not _is_tensor(perm) or perm.dtype != torch.int32:
+        raise TypeError(f"{what}: perm must be an int32 tensor" + (" or None" if optional else ""))
+    if perm.device != dev or not perm.is_contiguous() or perm.dim() != 1 or perm.numel() != m:
+        raise ValueError(f"{what}: perm must be a contiguous vector of A's {m} rows on A's device")
 
 
 def _ilu0_plan(a):
@@ -1734,21 +1725,17 @@ def _ilu0_plan(a):
     if st == _capi.INVALID_VALUE:
         raise ValueError("ilu0_inspect: every row must hold strictly ascending columns inside [0, m) and its diagonal entry")
     check(st, "ilu0_inspect")
-    return _Ilu0Plan(hd, plan, _ilu0_key(a), (a.rowptr(), a.colind()))
+    return _Ilu0Plan(hd, plan, _structure_key(a), (a.rowptr(), a.colind()))
 
 
 def ilu0_inspect(*args):
     """ilu0_inspect(a) -> operation_info_t, or ilu0_inspect(info, a): checks A's structure (sorted rows, stored diagonal;
     ValueError otherwise) and builds the level plan of the factorisation.  Synchronises the stream."""
-    if len(args) == 2:
-        info, a = args
-        ret = False
-    elif len(args) == 1:
-        a, = args
-        info, ret = operation_info_t(), True
-    else:
-        raise TypeError("expected (a) or (info, a)")
-    a = _ilu0_operand(a, "ilu0_inspect")
+    info, (a,) = _leading_info(args, 1, "a")
+    ret = info is None
+    if ret:
+        info = operation_info_t()
+    a = _square_csr_operand(a, "ilu0_inspect")
     info.state_ = _ilu0_plan(a)
     return info if ret else None
 
@@ -1773,7 +1760,7 @@ def _ilu0_lu_values(a, lu, what):
 def _ilu0_plan_of(info, a):
     """The inspect result in `info` if it is this pattern's, else a new one (stored into `info`)."""
     plan = info.state_ if info is not None and isinstance(info.state_, _Ilu0Plan) else None
-    if plan is None or plan.key != _ilu0_key(a):
+    if plan is None or plan.key != _structure_key(a):
         plan = _ilu0_plan(a)  # no usable inspect result: analyse now
         if info is not None:
             info.state_ = plan
@@ -1787,14 +1774,8 @@ def ilu0(*args):
     and U on and right of it: the one view serves triangular_solve(lu, lower_triangle, implicit_unit_diagonal, b, y) and
     triangular_solve(lu, upper_triangle, explicit_diagonal, y, x).  Nothing is synchronised; ilu0_status(info) tells afterwards
     whether a pivot was zero or not finite."""
-    if len(args) == 3:
-        info, a, lu = args
-    elif len(args) == 2:
-        a, lu = args
-        info = None
-    else:
-        raise TypeError("expected (a, lu) or (info, a, lu)")
-    a = _ilu0_operand(a, "ilu0")
+    info, (a, lu) = _leading_info(args, 2, "a, lu")
+    a = _square_csr_operand(a, "ilu0")
     lv = _ilu0_lu_values(a, lu, "ilu0")
     plan = _ilu0_plan_of(info, a)
     hd = _Handle.current(a.rowptr().device)
@@ -1813,14 +1794,8 @@ def ilu0_sweeps(*args):
     is no in-place form (ValueError).  `work` is a contiguous tensor of A's dtype and device with at least a.size() elements
     (unspecified afterwards), or None when sweeps <= 1.  Nothing is synchronised; ilu0_status(info) reports on the final
     pivots of the last sweep.  Without a usable inspect result the call analyses as ilu0 does."""
-    if len(args) == 5:
-        info, a, lu, work, sweeps = args
-    elif len(args) == 4:
-        a, lu, work, sweeps = args
-        info = None
-    else:
-        raise TypeError("expected (a, lu, work, sweeps) or (info, a, lu, work, sweeps)")
-    a = _ilu0_operand(a, "ilu0_sweeps")
+    info, (a, lu, work, sweeps) = _leading_info(args, 4, "a, lu, work, sweeps")
+    a = _square_csr_operand(a, "ilu0_sweeps")
     lv = _ilu0_lu_values(a, lu, "ilu0_sweeps")
     if isinstance(sweeps, bool) or not isinstance(sweeps, int):
         raise TypeError("ilu0_sweeps: sweeps must be an int")
@@ -1879,7 +1854,7 @@ def multicolor_order(a):
     have at most info()['colors'] levels for ilu0 / triangular_solve -- at the price of a weaker ILU(0) preconditioner than in
     the natural order.  `a` is a square plain csr_view (float32 / float64 values, int32 offsets and columns; rows need not be
     sorted, the pattern need not be symmetric).  Inspect-class: synchronises the stream, refused inside a capture."""
-    a = _ilu0_operand(a, "multicolor_order")
+    a = _square_csr_operand(a, "multicolor_order")
     dev = a.rowptr().device
     hd = _Handle.current(dev)
     m = a.shape()[0]
@@ -1901,29 +1876,16 @@ def multicolor_order(a):
     return multicolor_order_t(perm, inverse, color, color_ptr, info)
 
 
-class _PermutePlan:
+class _PermutePlan(_NativePlan):
     """permute_inspect state: the source position of every entry of B (spblas_gfx950_csr_permute_create)."""
-
-    def __init__(self, hd, plan, key, tensors):
-        self.hd, self.plan, self.key, self.tensors = hd, plan, key, tensors
-
-    def __del__(self):
-        try:
-            if self.plan:
-                _capi.lib().spblas_gfx950_csr_permute_destroy(self.hd.h, self.plan)
-                self.plan = None
-        except Exception:
-            pass
+    _destroy = "spblas_gfx950_csr_permute_destroy"
 
 
 def _permute_operands(a, perm, b, what):
-    a = _ilu0_operand(a, what)
+    a = _square_csr_operand(a, what)
     m, nnz = a.shape()[0], a.size()
     dev = a.rowptr().device
-    if not _is_tensor(perm) or perm.dtype != torch.int32:
-        raise TypeError(f"{what}: perm must be an int32 tensor")
-    if perm.device != dev or not perm.is_contiguous() or perm.dim() != 1 or perm.numel() != m:
-        raise ValueError(f"{what}: perm must be a contiguous vector of A's {m} rows on A's device")
+    _perm_vector(perm, m, dev, what)
     if not isinstance(b, csr_view):
         raise TypeError(f"{what}: b must be a plain csr_view over caller-allocated arrays, got {type(b).__name__}")
     bv, br, bc = b.values(), b.rowptr(), b.colind()
@@ -1970,14 +1932,10 @@ def permute_inspect(*args):
     A with column c renamed to the new index of c, columns ascending, equal columns in source order -- into b's row offsets and
     columns, and keeps the source position of every entry.  `b` is a csr_view over caller-allocated arrays (m + 1 offsets, nnz
     columns and values) as for transpose.  Inspect-class: allocates, synchronises the stream, refused inside a capture."""
-    if len(args) == 4:
-        info, a, perm, b = args
-        ret = False
-    elif len(args) == 3:
-        a, perm, b = args
-        info, ret = operation_info_t(), True
-    else:
-        raise TypeError("expected (a, perm, b) or (info, a, perm, b)")
+    info, (a, perm, b) = _leading_info(args, 3, "a, perm, b")
+    ret = info is None
+    if ret:
+        info = operation_info_t()
     a = _permute_operands(a, perm, b, "permute_inspect")
     info.state_ = _permute_plan(a, perm, b)
     info.update_impl_(a.shape(), a.size())
@@ -1989,13 +1947,7 @@ def permute(*args):
     b's values.  With the info of permute_inspect for these arrays it only gathers the values, b.values[p] = a.values[source of
     p]: one launch, nothing allocated or synchronised, so it can be recorded in a graph -- the refresh after A's values changed
     on a fixed pattern.  An info that was made for other arrays is replaced by a new inspect."""
-    if len(args) == 4:
-        info, a, perm, b = args
-    elif len(args) == 3:
-        a, perm, b = args
-        info = None
-    else:
-        raise TypeError("expected (a, perm, b) or (info, a, perm, b)")
+    info, (a, perm, b) = _leading_info(args, 3, "a, perm, b")
     a = _permute_operands(a, perm, b, "permute")
     plan = info.state_ if info is not None and isinstance(info.state_, _PermutePlan) else None
     if plan is None or plan.key != _permute_key(a, perm, b):
@@ -2035,32 +1987,14 @@ def permute_vector(perm, src, dst, inverse=False):
 
 
 # ---- multicolour Gauss-Seidel / SOR / SSOR sweeps (spblas_gfx950_gs_*; no reference counterpart) ----
-class _GsPlan:
+class _GsPlan(_NativePlan):
     """gauss_seidel_inspect state: the colour offsets, the position of every row's diagonal entry and the row order
     (spblas_gfx950_gs_create).  Structure only, no values."""
-
-    def __init__(self, hd, plan, key, tensors):
-        self.hd, self.plan, self.key, self.tensors = hd, plan, key, tensors
-
-    def info(self):
-        arr = (ctypes.c_int64 * 4)()
-        check(_capi.lib().spblas_gfx950_gs_info(self.plan, arr), "spblas_gfx950_gs_info")
-        return dict(zip(("colors", "max_color_size", "lanes_per_row", "launches_per_forward_sweep"), list(arr)))
-
-    def __del__(self):
-        try:
-            if self.plan:
-                _capi.lib().spblas_gfx950_gs_destroy(self.hd.h, self.plan)
-                self.plan = None
-        except Exception:
-            pass
+    _destroy, _info_call = "spblas_gfx950_gs_destroy", "spblas_gfx950_gs_info"
+    _info_names = ("colors", "max_color_size", "lanes_per_row", "launches_per_forward_sweep")
 
 
 _GS_DIRECTIONS = {"forward": _capi.GS_FORWARD, "backward": _capi.GS_BACKWARD, "symmetric": _capi.GS_SYMMETRIC}
-
-
-def _gs_key(a):
-    return (a.rowptr().data_ptr(), a.colind().data_ptr(), tuple(a.shape()), a.size())
 
 
 def gauss_seidel_inspect(*args, perm=None):
@@ -2084,18 +2018,14 @@ def gauss_seidel_inspect(*args, perm=None):
     else:
         raise TypeError("expected (a, color_ptr, perm=None) or (info, a, color_ptr, perm=None)")
     what = "gauss_seidel_inspect"
-    a = _ilu0_operand(a, what)
+    a = _square_csr_operand(a, what)
     m = a.shape()[0]
     dev = a.rowptr().device
     if not _is_tensor(color_ptr) or color_ptr.dtype != torch.int32:
         raise TypeError(f"{what}: color_ptr must be an int32 tensor")
     if color_ptr.device != dev or not color_ptr.is_contiguous() or color_ptr.dim() != 1 or color_ptr.numel() < 1:
         raise ValueError(f"{what}: color_ptr must be a contiguous vector of colours + 1 offsets on A's device")
-    if perm is not None:
-        if not _is_tensor(perm) or perm.dtype != torch.int32:
-            raise TypeError(f"{what}: perm must be an int32 tensor or None")
-        if perm.device != dev or not perm.is_contiguous() or perm.dim() != 1 or perm.numel() != m:
-            raise ValueError(f"{what}: perm must be a contiguous vector of A's {m} rows on A's device")
+    _perm_vector(perm, m, dev, what, optional=True)
     hd = _Handle.current(dev)
     plan = ctypes.c_void_p()
     st = _capi.lib().spblas_gfx950_gs_create(hd.h, ctypes.byref(plan), m, a.size(), _ptr(a.rowptr()), _ptr(a.colind()),
@@ -2105,7 +2035,7 @@ def gauss_seidel_inspect(*args, perm=None):
                          "the row offsets must describe the entries with every column inside [0, m), every row must store "
                          "exactly one diagonal entry and no off-diagonal entry may join two rows of one colour")
     check(st, what)
-    info.state_ = _GsPlan(hd, plan, _gs_key(a), (a.rowptr(), a.colind()))
+    info.state_ = _GsPlan(hd, plan, _structure_key(a), (a.rowptr(), a.colind()))
     info.update_impl_(a.shape(), a.size())
     return info if ret else None
 
@@ -2125,7 +2055,7 @@ def gauss_seidel(info, a, b, x, sweeps=1, omega=1.0, direction="forward"):
     given.  Not offered: a block of right-hand sides, weighted Jacobi, an implied zero initial guess, several colours per
     launch, scaled / complex / 16-bit / int64 / csc_view operands, distance-2 colourings."""
     what = "gauss_seidel"
-    a = _ilu0_operand(a, what)
+    a = _square_csr_operand(a, what)
     m = a.shape()[0]
     av = a.values()
     for name, t in (("b", b), ("x", x)):
@@ -2148,7 +2078,7 @@ def gauss_seidel(info, a, b, x, sweeps=1, omega=1.0, direction="forward"):
     if not isinstance(direction, str) or direction not in _GS_DIRECTIONS:
         raise ValueError(f"{what}: direction must be 'forward', 'backward' or 'symmetric'")
     plan = getattr(info, "state_", None)
-    if not isinstance(plan, _GsPlan) or plan.key != _gs_key(a):
+    if not isinstance(plan, _GsPlan) or plan.key != _structure_key(a):
         raise ValueError(f"{what}: info must be the result of gauss_seidel_inspect for these row offsets and columns")
     hd = _Handle.current(a.rowptr().device)
     vt, ct = _vtype(av, what)

@@ -14,8 +14,8 @@
 // direction -- not on the grid, on earlier calls or on whether the launches were recorded in a graph.
 //
 // Kernel: a relative of trsv_sweep_kernel (sptrsv_sweeps.hip) that reads and writes the SAME vector, covers both triangles,
-// carries omega and walks one colour's range of the row order.  A group of G lanes owns a row (G by the rule of sptrsv_create
-// from nnz / m), strides its entries two per lane in flight and reduces in trsv_row's order (the bits depend on G alone);
+// carries omega and walks one colour's range of the row order.  A group of G lanes owns a row (G = lanes_per_row of
+// csr_inspect.hpp), strides its entries two per lane in flight and reduces in trsv_row's order (the bits depend on G alone);
 // lane 0 applies the update.  The groups of a capped grid stride over the colour's rows and load the NEXT row's index, entry
 // range, b and diagonal (through the plan's diagonal positions) while the current row is computed -- none of those loads
 // touches x.  x is one pointer, read and written, hence not __restrict__; a colour ends at a kernel boundary: plain loads and
@@ -25,6 +25,7 @@
 // colours per launch, scaled operands, complex / 16-bit values, int64 indices, CSC operands, distance-2 colourings.
 #include "common.hpp"
 #include "complex_api.hpp"
+#include "csr_inspect.hpp"
 #include "lowp_api.hpp"
 
 #include <algorithm>
@@ -124,36 +125,7 @@ __global__ __launch_bounds__(GS_THREADS) void gs_color_kernel(int first, int cou
   }
 }
 
-// ---- the inspect's checks.  flag[0] = 1 on a violation.
-__global__ __launch_bounds__(256) void gs_check_rows_kernel(int64_t m, int64_t nnz, const int32_t* __restrict__ rowptr,
-                                                            int32_t* __restrict__ flag) {
-  const int64_t r = (int64_t) blockIdx.x * 256 + threadIdx.x;
-  if (r >= m)
-    return;
-  const int64_t p0 = rowptr[r], p1 = rowptr[r + 1];
-  if (!(p0 >= 0 && p0 <= p1 && p1 <= nnz && (r > 0 || p0 == 0) && (r + 1 < m || p1 == nnz)))
-    flag[0] = 1;
-}
-__global__ __launch_bounds__(256) void gs_check_cols_kernel(int64_t m, int64_t nnz, const int32_t* __restrict__ colind,
-                                                            int32_t* __restrict__ flag) {
-  bool bad = false;
-  for (int64_t p = (int64_t) blockIdx.x * 256 + threadIdx.x; p < nnz; p += (int64_t) gridDim.x * 256) {
-    const int c = colind[p];
-    bad |= c < 0 || c >= m;
-  }
-  if (bad)
-    flag[0] = 1;
-}
-// the check of csr_permute_create (multicolor.hip: pm_check_perm_kernel): seen[] arrives filled with -1
-__global__ __launch_bounds__(256) void gs_check_perm_kernel(int64_t m, const int32_t* __restrict__ perm, int32_t* __restrict__ seen,
-                                                            int32_t* __restrict__ flag) {
-  const int64_t i = (int64_t) blockIdx.x * 256 + threadIdx.x;
-  if (i >= m)
-    return;
-  const int p = perm[i];
-  if (p < 0 || p >= m || atomicCAS(seen + p, -1, (int) i) != -1)
-    flag[0] = 1;
-}
+// ---- the inspect's checks (structure and perm: csr_inspect.hpp).  flag[0] = 1 on a violation.
 // color[sigma(i)] = the colour of position i: the last c with color_ptr[c] <= i (color_ptr checked on the host before)
 __global__ __launch_bounds__(256) void gs_row_color_kernel(int64_t m, int colours, const int32_t* __restrict__ color_ptr,
                                                            const int32_t* __restrict__ perm, int32_t* __restrict__ color) {
@@ -203,16 +175,11 @@ __global__ __launch_bounds__(256) void gs_check_entries_kernel(int64_t m, const 
   }
 }
 
-static unsigned gs_stride_grid(spblas_gfx950_handle_t h, int64_t n) {
-  const int64_t cap = (int64_t) (h->num_cus > 0 ? h->num_cus : 256) * 16;
-  return (unsigned) std::max<int64_t>(1, std::min(cap, cdiv(n, 256)));
-}
-
 template <typename T, int G>
 static int gs_sweep_typed(spblas_gfx950_handle_t h, const spblas_gfx950_gs_s* pl, int sweeps, int direction,
                           const int32_t* rowptr, const int32_t* colind, const T* values, T omega, const T* b, T* x) {
   constexpr int rows_per_block = GS_THREADS / G;
-  const int64_t grid_cap = (int64_t) (h->num_cus > 0 ? h->num_cus : 256) * GS_BLOCKS_PER_CU;
+  const int64_t grid_cap = (int64_t) cu_count(h) * GS_BLOCKS_PER_CU;
   const int relax = omega == T(1) ? 0 : 1;
   const int colours = (int) pl->colours;
   auto half = [&](bool forward) {
@@ -244,12 +211,9 @@ static int gs_sweep_lanes(spblas_gfx950_handle_t h, const spblas_gfx950_gs_s* pl
   const T w = *static_cast<const T*>(omega);
   const T* bb = static_cast<const T*>(b);
   T* xx = static_cast<T*>(x);
-  switch (pl->lanes) {
-    case 4: return gs_sweep_typed<T, 4>(h, pl, sweeps, direction, rowptr, colind, v, w, bb, xx);
-    case 16: return gs_sweep_typed<T, 16>(h, pl, sweeps, direction, rowptr, colind, v, w, bb, xx);
-    case 64: return gs_sweep_typed<T, 64>(h, pl, sweeps, direction, rowptr, colind, v, w, bb, xx);
-    default: return gs_sweep_typed<T, 8>(h, pl, sweeps, direction, rowptr, colind, v, w, bb, xx);
-  }
+  return with_lanes(pl->lanes, [&](auto g) {
+    return gs_sweep_typed<T, decltype(g)::value>(h, pl, sweeps, direction, rowptr, colind, v, w, bb, xx);
+  });
 }
 
 } // namespace spb
@@ -272,13 +236,9 @@ int spblas_gfx950_gs_destroy(spblas_gfx950_handle_t handle, spblas_gfx950_gs_t p
 int spblas_gfx950_gs_create(spblas_gfx950_handle_t handle, spblas_gfx950_gs_t* plan_out, int64_t m, int64_t nnz,
                             const int32_t* rowptr, const int32_t* colind, int64_t colours, const int32_t* color_ptr,
                             const int32_t* perm) {
-  if (!handle)
-    return SPBLAS_GFX950_STATUS_INVALID_HANDLE;
-  if (stream_capturing(handle->stream))  // inspect-class call: never part of a graph
-    return SPBLAS_GFX950_STATUS_NOT_SUPPORTED;
-  if (!plan_out || !rowptr || !color_ptr || (nnz > 0 && !colind))
-    return SPBLAS_GFX950_STATUS_INVALID_POINTER;
-  if (m < 0 || nnz < 0 || m >= INT32_MAX || nnz > INT32_MAX || colours < 0 || colours >= INT32_MAX)
+  if (const int st = inspect_args_status(handle, plan_out && rowptr && color_ptr && (nnz <= 0 || colind), m, nnz))
+    return st;
+  if (colours < 0 || colours >= INT32_MAX)
     return SPBLAS_GFX950_STATUS_INVALID_SIZE;
   *plan_out = nullptr;
   if (m == 0 && nnz != 0)  // no offsets of an empty matrix describe entries
@@ -289,15 +249,12 @@ int spblas_gfx950_gs_create(spblas_gfx950_handle_t handle, spblas_gfx950_gs_t* p
   pl->m = m;
   pl->nnz = nnz;
   pl->colours = colours;
-  const double avg = m > 0 ? (double) nnz / (double) m : 0.0;
-  pl->lanes = avg > 96 ? 64 : (avg > 24 ? 16 : (avg > 6 ? 8 : 4));  // the rule of spblas_gfx950_sptrsv_create
+  pl->lanes = lanes_per_row(m, nnz);
   hipStream_t s = handle->stream;
+  dev_temps temps(s);
   int32_t *flag = nullptr, *seen = nullptr, *color = nullptr;
   auto fail = [&](int code) {
     (void) hipStreamSynchronize(s);
-    dev_free(flag, s);
-    dev_free(seen, s);
-    dev_free(color, s);
     (void) spblas_gfx950_gs_destroy(handle, pl);
     return code;
   };
@@ -325,8 +282,8 @@ int spblas_gfx950_gs_create(spblas_gfx950_handle_t handle, spblas_gfx950_gs_t* p
     return SPBLAS_GFX950_STATUS_SUCCESS;
   }
   int rc;
-  if ((rc = dev_alloc((void**) &flag, 16, s)) || (rc = dev_alloc((void**) &color, (size_t) m * 4, s)) ||
-      (rc = dev_alloc((void**) &pl->diag, (size_t) m * 4, s)) || (perm && (rc = dev_alloc((void**) &seen, (size_t) m * 4, s))) ||
+  if ((rc = temps.alloc(&flag, 16)) || (rc = temps.alloc(&color, (size_t) m * 4)) ||
+      (rc = dev_alloc((void**) &pl->diag, (size_t) m * 4, s)) || (perm && (rc = temps.alloc(&seen, (size_t) m * 4))) ||
       (perm && (rc = dev_alloc((void**) &pl->perm, (size_t) m * 4, s))))
     return fail(rc);
   if ((e = hipMemsetAsync(flag, 0, 16, s)) != hipSuccess ||
@@ -335,28 +292,17 @@ int spblas_gfx950_gs_create(spblas_gfx950_handle_t handle, spblas_gfx950_gs_t* p
   // perm and the structure are checked, with a synchronisation, BEFORE anything indexes with them
   const dim3 rows_grid((unsigned) cdiv(m, 256)), block(256);
   if (perm)
-    hipLaunchKernelGGL(gs_check_perm_kernel, rows_grid, block, 0, s, m, perm, seen, flag);
-  hipLaunchKernelGGL(gs_check_rows_kernel, rows_grid, block, 0, s, m, nnz, rowptr, flag);
-  if (nnz > 0)
-    hipLaunchKernelGGL(gs_check_cols_kernel, dim3(gs_stride_grid(handle, nnz)), block, 0, s, m, nnz, colind, flag);
-  int32_t bad = 0;
-  if ((e = hipGetLastError()) != hipSuccess || (e = hipMemcpyAsync(&bad, flag, 4, hipMemcpyDeviceToHost, s)) != hipSuccess ||
-      (e = hipStreamSynchronize(s)) != hipSuccess)
-    return fail(hip_fail(e));
-  if (bad)
-    return fail(SPBLAS_GFX950_STATUS_INVALID_VALUE);
+    hipLaunchKernelGGL(check_perm_kernel, rows_grid, block, 0, s, m, perm, seen, flag);
+  if ((rc = check_csr_structure(handle, m, nnz, rowptr, colind, flag)))
+    return fail(rc);
   // one diagonal entry per row, no entry inside a colour
   hipLaunchKernelGGL(gs_row_color_kernel, rows_grid, block, 0, s, m, (int) colours, color_ptr, perm, color);
   hipLaunchKernelGGL(gs_check_entries_kernel, dim3((unsigned) cdiv(m, 32)), block, 0, s, m, rowptr, colind, color, pl->diag, flag);
   if ((e = hipGetLastError()) != hipSuccess ||
-      (perm && (e = hipMemcpyAsync(pl->perm, perm, (size_t) m * 4, hipMemcpyDeviceToDevice, s)) != hipSuccess) ||
-      (e = hipMemcpyAsync(&bad, flag, 4, hipMemcpyDeviceToHost, s)) != hipSuccess || (e = hipStreamSynchronize(s)) != hipSuccess)
+      (perm && (e = hipMemcpyAsync(pl->perm, perm, (size_t) m * 4, hipMemcpyDeviceToDevice, s)) != hipSuccess))
     return fail(hip_fail(e));
-  if (bad)
-    return fail(SPBLAS_GFX950_STATUS_INVALID_VALUE);
-  dev_free(flag, s);
-  dev_free(seen, s);
-  dev_free(color, s);
+  if ((rc = read_flag(handle, flag)))
+    return fail(rc);
   *plan_out = pl;
   return SPBLAS_GFX950_STATUS_SUCCESS;
 }

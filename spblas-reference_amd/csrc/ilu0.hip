@@ -35,6 +35,7 @@
 // from the previous iterate, no hand-off between levels; levels - 1 sweeps give the bits of the schedule above.
 #include "common.hpp"
 #include "complex_api.hpp"
+#include "csr_inspect.hpp"
 #include "lowp_api.hpp"
 #include "trsv_plan.hpp"
 
@@ -329,7 +330,7 @@ __global__ __launch_bounds__(256) void ilu0_check_kernel(int64_t m, int64_t nnz,
     return;
   const int64_t p0 = rowptr[r], p1 = rowptr[r + 1];
   int d = -1;
-  bool ok = p0 >= 0 && p0 <= p1 && p1 <= nnz && (r > 0 || p0 == 0) && (r + 1 < m || p1 == nnz);
+  bool ok = row_offsets_ok(r, m, nnz, p0, p1);
   if (ok) {
     int64_t prev = -1;
     for (int64_t p = p0; p < p1; ++p) {
@@ -423,14 +424,8 @@ int spblas_gfx950_ilu0_destroy(spblas_gfx950_handle_t handle, spblas_gfx950_ilu0
 
 int spblas_gfx950_ilu0_create(spblas_gfx950_handle_t handle, spblas_gfx950_ilu0_t* plan_out, int64_t m, int64_t nnz,
                               const int32_t* rowptr, const int32_t* colind) {
-  if (!handle)
-    return SPBLAS_GFX950_STATUS_INVALID_HANDLE;
-  if (stream_capturing(handle->stream))  // inspect-class call: never part of a graph
-    return SPBLAS_GFX950_STATUS_NOT_SUPPORTED;
-  if (!plan_out || !rowptr || (nnz > 0 && !colind))
-    return SPBLAS_GFX950_STATUS_INVALID_POINTER;
-  if (m < 0 || nnz < 0 || m >= INT32_MAX || nnz > INT32_MAX)
-    return SPBLAS_GFX950_STATUS_INVALID_SIZE;
+  if (const int st = inspect_args_status(handle, plan_out && rowptr && (nnz <= 0 || colind), m, nnz))
+    return st;
   *plan_out = nullptr;
   auto* pl = new (std::nothrow) spblas_gfx950_ilu0_s();
   if (!pl)
@@ -440,15 +435,15 @@ int spblas_gfx950_ilu0_create(spblas_gfx950_handle_t handle, spblas_gfx950_ilu0_
   pl->rowptr = rowptr;
   pl->colind = colind;
   hipStream_t s = handle->stream;
+  dev_temps temps(s);
   int32_t* flag = nullptr;
   auto fail = [&](int code) {
     (void) hipStreamSynchronize(s);
-    dev_free(flag, s);
     (void) spblas_gfx950_ilu0_destroy(handle, pl);
     return code;
   };
   int rc;
-  if ((rc = dev_alloc((void**) &pl->status, 16, s)) || (rc = dev_alloc((void**) &flag, 16, s)) ||
+  if ((rc = dev_alloc((void**) &pl->status, 16, s)) || (rc = temps.alloc(&flag, 16)) ||
       (rc = dev_alloc((void**) &pl->diag, (size_t) m * 4, s)))
     return fail(rc);
   hipError_t e = hipMemsetAsync(pl->status, 0, 16, s);
@@ -463,17 +458,12 @@ int spblas_gfx950_ilu0_create(spblas_gfx950_handle_t handle, spblas_gfx950_ilu0_
     if ((e = hipGetLastError()) != hipSuccess)
       return fail(hip_fail(e));
   }
-  int32_t bad = 0;
-  if ((e = hipMemcpyAsync(&bad, flag, 4, hipMemcpyDeviceToHost, s)) != hipSuccess ||
-      (e = hipStreamSynchronize(s)) != hipSuccess)
-    return fail(hip_fail(e));
-  if (bad != 0)
-    return fail(SPBLAS_GFX950_STATUS_INVALID_VALUE);
+  if ((rc = read_flag(handle, flag)))
+    return fail(rc);
   // the dependency graph of ILU(0) is the one of the lower solve: its level plan, built by the existing code
   if ((rc = spblas_gfx950_sptrsv_create(handle, &pl->levels, m, nnz, rowptr, colind, SPBLAS_GFX950_LOWER,
                                         SPBLAS_GFX950_DIAG_UNIT)))
     return fail(rc);
-  dev_free(flag, s);
   *plan_out = pl;
   return SPBLAS_GFX950_STATUS_SUCCESS;
 }

@@ -19,7 +19,7 @@
 // colour written earlier in the same launch may be seen (fewer rounds); a stale -1 only delays a vertex.  The uncoloured vertex of
 // the largest key never waits, so every round colours at least one vertex: at most m rounds.
 //
-// Row work: a TEAM of G lanes of one wavefront owns a vertex (G by the rule of spblas_gfx950_sptrsv_create from nnz / m).  Every
+// Row work: a TEAM of G lanes of one wavefront owns a vertex (G = lanes_per_row(m, nnz), csr_inspect.hpp).  Every
 // lane keeps a 64-bit mask of the colours base .. base + 63 it met; the masks are OR-reduced over the team by shuffles.  A full
 // window moves base on by 64 and the neighbours are scanned again: nothing is sized by the degree.
 //
@@ -33,6 +33,7 @@
 // their source order.  The payload of the second pass is the plan's entry map; csr_permute_values is one gather through it.
 #include "common.hpp"
 #include "complex_api.hpp"
+#include "csr_inspect.hpp"
 #include "lowp_api.hpp"
 #include "scan.hpp"
 
@@ -142,28 +143,7 @@ __global__ __launch_bounds__(MC_THREADS) void mc_round_kernel(mc_args a) {
   }
 }
 
-// Structure checks of the two inspects.  flag[0] = 1 when the offsets do not describe nnz entries ...
-__global__ __launch_bounds__(256) void mc_check_rows_kernel(int64_t m, int64_t nnz, const int32_t* __restrict__ rowptr,
-                                                            int32_t* __restrict__ flag) {
-  const int64_t r = (int64_t) blockIdx.x * 256 + threadIdx.x;
-  if (r >= m)
-    return;
-  const int64_t p0 = rowptr[r], p1 = rowptr[r + 1];
-  if (!(p0 >= 0 && p0 <= p1 && p1 <= nnz && (r > 0 || p0 == 0) && (r + 1 < m || p1 == nnz)))
-    flag[0] = 1;
-}
-// ... or a column lies outside [0, m)
-__global__ __launch_bounds__(256) void mc_check_cols_kernel(int64_t m, int64_t nnz, const int32_t* __restrict__ colind,
-                                                            int32_t* __restrict__ flag) {
-  bool bad = false;
-  for (int64_t p = (int64_t) blockIdx.x * 256 + threadIdx.x; p < nnz; p += (int64_t) gridDim.x * 256) {
-    const int c = colind[p];
-    bad |= c < 0 || c >= m;
-  }
-  if (bad)
-    flag[0] = 1;
-}
-
+// (the structure and perm checks of the two inspects: csr_inspect.hpp)
 __global__ __launch_bounds__(256) void mc_iota_kernel(int64_t n, int32_t* __restrict__ out) {
   const int64_t i = (int64_t) blockIdx.x * 256 + threadIdx.x;
   if (i < n)
@@ -175,17 +155,6 @@ __global__ __launch_bounds__(256) void mc_invert_kernel(int64_t m, const int32_t
   const int64_t i = (int64_t) blockIdx.x * 256 + threadIdx.x;
   if (i < m)
     inv[perm[i]] = (int32_t) i;
-}
-
-// inv[] arrives filled with -1.  flag[0] = 1 when perm holds an index outside [0, m) or one index twice; else inv = perm^-1.
-__global__ __launch_bounds__(256) void pm_check_perm_kernel(int64_t m, const int32_t* __restrict__ perm, int32_t* __restrict__ inv,
-                                                            int32_t* __restrict__ flag) {
-  const int64_t i = (int64_t) blockIdx.x * 256 + threadIdx.x;
-  if (i >= m)
-    return;
-  const int p = perm[i];
-  if (p < 0 || p >= m || atomicCAS(inv + p, -1, (int) i) != -1)
-    flag[0] = 1;
 }
 
 __global__ __launch_bounds__(256) void pm_row_len_kernel(int64_t m, const int32_t* __restrict__ perm,
@@ -226,35 +195,11 @@ __global__ __launch_bounds__(256) void pm_scatter_kernel(int64_t n, const int32_
     dst[map[p]] = src[p];
 }
 
-static unsigned stride_grid(spblas_gfx950_handle_t h, int64_t n) {
-  const int64_t cap = (int64_t) (h->num_cus > 0 ? h->num_cus : 256) * 16;
-  return (unsigned) std::max<int64_t>(1, std::min(cap, cdiv(n, 256)));
-}
-
-// The shared part of the two inspects: STATUS_INVALID_VALUE unless rowptr / colind describe an m x m matrix of nnz entries.
-// Synchronises the stream; flag = 16 zeroed device bytes of the caller's.
-static int check_structure(spblas_gfx950_handle_t h, int64_t m, int64_t nnz, const int32_t* rowptr, const int32_t* colind,
-                           int32_t* flag) {
-  hipStream_t s = h->stream;
-  if (m > 0)
-    hipLaunchKernelGGL(mc_check_rows_kernel, dim3((unsigned) cdiv(m, 256)), dim3(256), 0, s, m, nnz, rowptr, flag);
-  if (nnz > 0)
-    hipLaunchKernelGGL(mc_check_cols_kernel, dim3(stride_grid(h, nnz)), dim3(256), 0, s, m, nnz, colind, flag);
-  SPB_HIP(hipGetLastError());
-  int32_t bad = 0;
-  SPB_HIP(hipMemcpyAsync(&bad, flag, 4, hipMemcpyDeviceToHost, s));
-  SPB_HIP(hipStreamSynchronize(s));
-  return bad != 0 ? SPBLAS_GFX950_STATUS_INVALID_VALUE : SPBLAS_GFX950_STATUS_SUCCESS;
-}
-
-static void launch_round(hipStream_t s, int G, const mc_args& a) {
-  const dim3 grid((unsigned) cdiv(a.m, MC_THREADS / G)), block(MC_THREADS);
-  switch (G) {
-  case 64: hipLaunchKernelGGL(mc_round_kernel<64>, grid, block, 0, s, a); break;
-  case 16: hipLaunchKernelGGL(mc_round_kernel<16>, grid, block, 0, s, a); break;
-  case 8: hipLaunchKernelGGL(mc_round_kernel<8>, grid, block, 0, s, a); break;
-  default: hipLaunchKernelGGL(mc_round_kernel<4>, grid, block, 0, s, a); break;
-  }
+static void launch_round(hipStream_t s, int lanes, const mc_args& a) {
+  with_lanes(lanes, [&](auto g) {
+    constexpr int G = decltype(g)::value;
+    hipLaunchKernelGGL(mc_round_kernel<G>, dim3((unsigned) cdiv(a.m, MC_THREADS / G)), dim3(MC_THREADS), 0, s, a);
+  });
 }
 
 } // namespace spb
@@ -278,14 +223,8 @@ int spblas_gfx950_multicolor_destroy(spblas_gfx950_handle_t handle, spblas_gfx95
 
 int spblas_gfx950_multicolor_create(spblas_gfx950_handle_t handle, spblas_gfx950_multicolor_t* plan_out, int64_t m, int64_t nnz,
                                     const int32_t* rowptr, const int32_t* colind) {
-  if (!handle)
-    return SPBLAS_GFX950_STATUS_INVALID_HANDLE;
-  if (stream_capturing(handle->stream))  // inspect-class call: never part of a graph
-    return SPBLAS_GFX950_STATUS_NOT_SUPPORTED;
-  if (!plan_out || !rowptr || (nnz > 0 && !colind))
-    return SPBLAS_GFX950_STATUS_INVALID_POINTER;
-  if (m < 0 || nnz < 0 || m >= INT32_MAX || nnz > INT32_MAX)
-    return SPBLAS_GFX950_STATUS_INVALID_SIZE;
+  if (const int st = inspect_args_status(handle, plan_out && rowptr && (nnz <= 0 || colind), m, nnz))
+    return st;
   *plan_out = nullptr;
   if (m == 0 && nnz != 0)  // no offsets of an empty matrix describe entries
     return SPBLAS_GFX950_STATUS_INVALID_VALUE;
@@ -294,19 +233,13 @@ int spblas_gfx950_multicolor_create(spblas_gfx950_handle_t handle, spblas_gfx950
     return SPBLAS_GFX950_STATUS_ALLOC_FAILED;
   pl->m = m;
   pl->nnz = nnz;
-  const double avg = m > 0 ? (double) nnz / (double) m : 0.0;
-  pl->lanes = avg > 96 ? 64 : (avg > 24 ? 16 : (avg > 6 ? 8 : 4));  // the rule of spblas_gfx950_sptrsv_create
+  pl->lanes = lanes_per_row(m, nnz);
   hipStream_t s = handle->stream;
+  dev_temps temps(s);
   int32_t *flag = nullptr, *t_rowptr = nullptr, *t_colind = nullptr, *junk = nullptr, *iota = nullptr;
   unsigned* counters = nullptr;
   auto fail = [&](int code) {
     (void) hipStreamSynchronize(s);
-    dev_free(flag, s);
-    dev_free(counters, s);
-    dev_free(t_rowptr, s);
-    dev_free(t_colind, s);
-    dev_free(junk, s);
-    dev_free(iota, s);
     (void) spblas_gfx950_multicolor_destroy(handle, pl);
     return code;
   };
@@ -322,7 +255,7 @@ int spblas_gfx950_multicolor_create(spblas_gfx950_handle_t handle, spblas_gfx950
   }
   dev_free(pl->color_ptr, s);  // sized once the colours are counted
   pl->color_ptr = nullptr;
-  if ((rc = dev_alloc((void**) &flag, 16, s)) || (rc = dev_alloc((void**) &counters, 16, s)) ||
+  if ((rc = temps.alloc(&flag, 16)) || (rc = temps.alloc(&counters, 16)) ||
       (rc = dev_alloc((void**) &pl->color, (size_t) m * 4, s)) || (rc = dev_alloc((void**) &pl->perm, (size_t) m * 4, s)) ||
       (rc = dev_alloc((void**) &pl->inv_perm, (size_t) m * 4, s)))
     return fail(rc);
@@ -330,12 +263,12 @@ int spblas_gfx950_multicolor_create(spblas_gfx950_handle_t handle, spblas_gfx950
       (e = hipMemsetAsync(pl->color, 0xFF, (size_t) m * 4, s)) != hipSuccess)
     return fail(hip_fail(e));
   // the structure is checked, with a synchronisation of its own, BEFORE the transpose sees it
-  if ((rc = check_structure(handle, m, nnz, rowptr, colind, flag)))
+  if ((rc = check_csr_structure(handle, m, nnz, rowptr, colind, flag)))
     return fail(rc);
   // the pattern of A^T; the transpose moves 4-byte values along, here the columns themselves, into a buffer nobody reads
   const size_t junk_n = (size_t) std::max(m, nnz);
-  if ((rc = dev_alloc((void**) &t_rowptr, (size_t) (m + 1) * 4, s)) || (rc = dev_alloc((void**) &t_colind, (size_t) nnz * 4, s)) ||
-      (rc = dev_alloc((void**) &junk, junk_n * 4, s)) || (rc = dev_alloc((void**) &iota, (size_t) (m + 1) * 4, s)))
+  if ((rc = temps.alloc(&t_rowptr, (size_t) (m + 1) * 4)) || (rc = temps.alloc(&t_colind, (size_t) nnz * 4)) ||
+      (rc = temps.alloc(&junk, junk_n * 4)) || (rc = temps.alloc(&iota, (size_t) (m + 1) * 4)))
     return fail(rc);
   if ((rc = spblas_gfx950_csr_transpose(handle, m, m, nnz, rowptr, colind, colind, t_rowptr, t_colind, junk,
                                         SPBLAS_GFX950_F32)))
@@ -381,12 +314,6 @@ int spblas_gfx950_multicolor_create(spblas_gfx950_handle_t handle, spblas_gfx950
     return fail(hip_fail(e));
   for (int64_t c = 0; c < pl->colours; ++c)
     pl->largest = std::max<int64_t>(pl->largest, h_ptr[c + 1] - h_ptr[c]);
-  dev_free(flag, s);
-  dev_free(counters, s);
-  dev_free(t_rowptr, s);
-  dev_free(t_colind, s);
-  dev_free(junk, s);
-  dev_free(iota, s);
   *plan_out = pl;
   return SPBLAS_GFX950_STATUS_SUCCESS;
 }
@@ -433,14 +360,9 @@ int spblas_gfx950_csr_permute_destroy(spblas_gfx950_handle_t handle, spblas_gfx9
 int spblas_gfx950_csr_permute_create(spblas_gfx950_handle_t handle, spblas_gfx950_permute_t* plan_out, int64_t m, int64_t nnz,
                                      const int32_t* rowptr, const int32_t* colind, const int32_t* perm, int32_t* b_rowptr,
                                      int32_t* b_colind) {
-  if (!handle)
-    return SPBLAS_GFX950_STATUS_INVALID_HANDLE;
-  if (stream_capturing(handle->stream))  // inspect-class call: never part of a graph
-    return SPBLAS_GFX950_STATUS_NOT_SUPPORTED;
-  if (!plan_out || !rowptr || !b_rowptr || (m > 0 && !perm) || (nnz > 0 && (!colind || !b_colind)))
-    return SPBLAS_GFX950_STATUS_INVALID_POINTER;
-  if (m < 0 || nnz < 0 || m >= INT32_MAX || nnz > INT32_MAX)
-    return SPBLAS_GFX950_STATUS_INVALID_SIZE;
+  if (const int st = inspect_args_status(
+          handle, plan_out && rowptr && b_rowptr && (m <= 0 || perm) && (nnz <= 0 || (colind && b_colind)), m, nnz))
+    return st;
   *plan_out = nullptr;
   if (m == 0 && nnz != 0)
     return SPBLAS_GFX950_STATUS_INVALID_VALUE;
@@ -452,19 +374,12 @@ int spblas_gfx950_csr_permute_create(spblas_gfx950_handle_t handle, spblas_gfx95
   pl->m = m;
   pl->nnz = nnz;
   hipStream_t s = handle->stream;
+  dev_temps temps(s);
   int32_t *flag = nullptr, *inv = nullptr, *c_col = nullptr, *c_pos = nullptr, *d_rowptr = nullptr, *d_col = nullptr,
           *d_pos = nullptr;
   long long* partials = nullptr;
   auto fail = [&](int code) {
     (void) hipStreamSynchronize(s);
-    dev_free(flag, s);
-    dev_free(inv, s);
-    dev_free(c_col, s);
-    dev_free(c_pos, s);
-    dev_free(d_rowptr, s);
-    dev_free(d_col, s);
-    dev_free(d_pos, s);
-    dev_free(partials, s);
     (void) spblas_gfx950_csr_permute_destroy(handle, pl);
     return code;
   };
@@ -476,15 +391,15 @@ int spblas_gfx950_csr_permute_create(spblas_gfx950_handle_t handle, spblas_gfx95
     return SPBLAS_GFX950_STATUS_SUCCESS;
   }
   int rc;
-  if ((rc = dev_alloc((void**) &flag, 16, s)) || (rc = dev_alloc((void**) &inv, (size_t) m * 4, s)))
+  if ((rc = temps.alloc(&flag, 16)) || (rc = temps.alloc(&inv, (size_t) m * 4)))
     return fail(rc);
   if ((e = hipMemsetAsync(flag, 0, 16, s)) != hipSuccess || (e = hipMemsetAsync(inv, 0xFF, (size_t) m * 4, s)) != hipSuccess)
     return fail(hip_fail(e));
   // perm and the structure are checked, with a synchronisation, BEFORE anything indexes with them or B is written
-  hipLaunchKernelGGL(pm_check_perm_kernel, dim3((unsigned) cdiv(m, 256)), dim3(256), 0, s, m, perm, inv, flag);
-  if ((rc = check_structure(handle, m, nnz, rowptr, colind, flag)))
+  hipLaunchKernelGGL(check_perm_kernel, dim3((unsigned) cdiv(m, 256)), dim3(256), 0, s, m, perm, inv, flag);
+  if ((rc = check_csr_structure(handle, m, nnz, rowptr, colind, flag)))
     return fail(rc);
-  if ((rc = dev_alloc((void**) &partials, (size_t) (cdiv(m, 2048) + 2) * sizeof(long long), s)))
+  if ((rc = temps.alloc(&partials, (size_t) (cdiv(m, 2048) + 2) * sizeof(long long))))
     return fail(rc);
   hipLaunchKernelGGL(pm_row_len_kernel, dim3((unsigned) cdiv(m, 256)), dim3(256), 0, s, m, perm, rowptr, b_rowptr);
   scan_counts_i32(s, m, b_rowptr, partials);
@@ -492,9 +407,8 @@ int spblas_gfx950_csr_permute_create(spblas_gfx950_handle_t handle, spblas_gfx95
     return fail(hip_fail(e));
   if (nnz > 0) {
     const size_t nb = (size_t) nnz * 4;
-    if ((rc = dev_alloc((void**) &pl->map, nb, s)) || (rc = dev_alloc((void**) &c_col, nb, s)) ||
-        (rc = dev_alloc((void**) &c_pos, nb, s)) || (rc = dev_alloc((void**) &d_col, nb, s)) ||
-        (rc = dev_alloc((void**) &d_pos, nb, s)) || (rc = dev_alloc((void**) &d_rowptr, (size_t) (m + 1) * 4, s)))
+    if ((rc = dev_alloc((void**) &pl->map, nb, s)) || (rc = temps.alloc(&c_col, nb)) || (rc = temps.alloc(&c_pos, nb)) ||
+        (rc = temps.alloc(&d_col, nb)) || (rc = temps.alloc(&d_pos, nb)) || (rc = temps.alloc(&d_rowptr, (size_t) (m + 1) * 4)))
       return fail(rc);
     hipLaunchKernelGGL(pm_fill_kernel, dim3((unsigned) cdiv(m, 32)), dim3(256), 0, s, m, perm, inv, rowptr, colind, b_rowptr,
                        c_col, c_pos);
@@ -509,14 +423,6 @@ int spblas_gfx950_csr_permute_create(spblas_gfx950_handle_t handle, spblas_gfx95
   }
   if ((e = hipStreamSynchronize(s)) != hipSuccess)
     return fail(hip_fail(e));
-  dev_free(flag, s);
-  dev_free(inv, s);
-  dev_free(c_col, s);
-  dev_free(c_pos, s);
-  dev_free(d_rowptr, s);
-  dev_free(d_col, s);
-  dev_free(d_pos, s);
-  dev_free(partials, s);
   *plan_out = pl;
   return SPBLAS_GFX950_STATUS_SUCCESS;
 }

@@ -29,6 +29,7 @@
 // reference's sequential loop: parity is norm-wise, not bit-wise.
 #include "common.hpp"
 #include "complex_api.hpp"
+#include "csr_inspect.hpp"
 #include "lowp_api.hpp"
 #include "scan.hpp"
 #include "trsv_plan.hpp"
@@ -615,7 +616,7 @@ __global__ __launch_bounds__(TRSV_BLOCK_THREADS) void trsv_chain_kernel(int l0, 
 int trsv_begin_solve(spblas_gfx950_handle_t h, spblas_gfx950_trsv_s* pl, bool* capturing_out, size_t* bar_off_out) {
   hipStream_t s = h->stream;
   const size_t ng = pl->groups.size();
-  const int cus = h->num_cus > 0 ? h->num_cus : 256;
+  const int cus = cu_count(h);
   // [ng + 1] = status word (the leading words are unused since the self-scheduling form left), then (32-int aligned) the
   // grid barrier: one line for the arrival counter and one release flag line per workgroup
   const size_t bar_off = (ng + 2 + 31) / 32 * 32, ctl_ints = bar_off + 32 * (size_t) (9 + 2 * cus);
@@ -658,7 +659,7 @@ static int trsv_solve_typed(spblas_gfx950_handle_t h, spblas_gfx950_trsv_s* pl, 
   const int upper = pl->uplo == SPBLAS_GFX950_UPPER, unit = pl->diag == SPBLAS_GFX950_DIAG_UNIT;
   const int m = (int) pl->m;
   const size_t ng = pl->groups.size();
-  const int cus = h->num_cus > 0 ? h->num_cus : 256;
+  const int cus = cu_count(h);
   bool capturing = false;
   size_t bar_off = 0;
   if (const int rc = trsv_begin_solve(h, pl, &capturing, &bar_off))
@@ -711,15 +712,19 @@ static int trsv_solve_typed(spblas_gfx950_handle_t h, spblas_gfx950_trsv_s* pl, 
   return SPBLAS_GFX950_STATUS_SUCCESS;
 }
 
+// The lanes-per-row rule of every solver-side plan and of the plan-free sweeps (declared in csr_inspect.hpp): the ONLY place it
+// is written.  m == 0 gives 4.
+int lanes_per_row(int64_t m, int64_t nnz) {
+  const double avg = m > 0 ? (double) nnz / (double) m : 0.0;
+  return avg > 96 ? 64 : (avg > 24 ? 16 : (avg > 6 ? 8 : 4));
+}
+
 template <typename T>
 static int trsv_solve_lanes(spblas_gfx950_handle_t h, spblas_gfx950_trsv_s* pl, const int32_t* rowptr,
                             const int32_t* colind, const T* values, T alpha, const T* b, T* x) {
-  switch (pl->lanes) {
-    case 4: return trsv_solve_typed<T, 4>(h, pl, rowptr, colind, values, alpha, b, x);
-    case 16: return trsv_solve_typed<T, 16>(h, pl, rowptr, colind, values, alpha, b, x);
-    case 64: return trsv_solve_typed<T, 64>(h, pl, rowptr, colind, values, alpha, b, x);
-    default: return trsv_solve_typed<T, 8>(h, pl, rowptr, colind, values, alpha, b, x);
-  }
+  return with_lanes(pl->lanes, [&](auto g) {
+    return trsv_solve_typed<T, decltype(g)::value>(h, pl, rowptr, colind, values, alpha, b, x);
+  });
 }
 
 } // namespace spb
@@ -730,14 +735,8 @@ extern "C" {
 
 int spblas_gfx950_sptrsv_create(spblas_gfx950_handle_t handle, spblas_gfx950_trsv_t* plan_out, int64_t m, int64_t nnz,
                                 const int32_t* rowptr, const int32_t* colind, int uplo, int diag) {
-  if (!handle)
-    return SPBLAS_GFX950_STATUS_INVALID_HANDLE;
-  if (stream_capturing(handle->stream))  // inspect-class call: sizes its output on the host, never part of a graph
-    return SPBLAS_GFX950_STATUS_NOT_SUPPORTED;
-  if (!plan_out || !rowptr || (nnz > 0 && !colind))
-    return SPBLAS_GFX950_STATUS_INVALID_POINTER;
-  if (m < 0 || nnz < 0 || m >= INT32_MAX || nnz > INT32_MAX)
-    return SPBLAS_GFX950_STATUS_INVALID_SIZE;
+  if (const int st = inspect_args_status(handle, plan_out && rowptr && (nnz <= 0 || colind), m, nnz))
+    return st;
   if ((uplo != SPBLAS_GFX950_LOWER && uplo != SPBLAS_GFX950_UPPER) ||
       (diag != SPBLAS_GFX950_DIAG_EXPLICIT && diag != SPBLAS_GFX950_DIAG_UNIT))
     return SPBLAS_GFX950_STATUS_INVALID_VALUE;
@@ -748,40 +747,28 @@ int spblas_gfx950_sptrsv_create(spblas_gfx950_handle_t handle, spblas_gfx950_trs
   pl->nnz = nnz;
   pl->uplo = uplo;
   pl->diag = diag;
-  const double avg = m > 0 ? (double) nnz / (double) m : 0.0;
-  pl->lanes = avg > 96 ? 64 : (avg > 24 ? 16 : (avg > 6 ? 8 : 4));
+  pl->lanes = lanes_per_row(m, nnz);
   *plan_out = pl;
   if (m == 0)
     return SPBLAS_GFX950_STATUS_SUCCESS;
 
   hipStream_t s = handle->stream;
   const int upper = uplo == SPBLAS_GFX950_UPPER;
+  dev_temps temps(s);
   int32_t *indeg = nullptr, *adj_ptr = nullptr, *cursor = nullptr, *adj = nullptr, *state = nullptr,
           *level_ptr = nullptr;
   long long* partials = nullptr;
   int rc = SPBLAS_GFX950_STATUS_SUCCESS;
   auto fail = [&](int code) {
     (void) hipStreamSynchronize(s);
-    dev_free(indeg, s);
-    dev_free(adj_ptr, s);
-    dev_free(cursor, s);
-    dev_free(adj, s);
-    dev_free(state, s);
-    dev_free(partials, s);
-    dev_free(level_ptr, s);
-    dev_free(pl->order, s);
-    dev_free(pl->level_ptr, s);
-    delete pl;
+    (void) spblas_gfx950_sptrsv_destroy(handle, pl);
     *plan_out = nullptr;
     return code;
   };
-  if ((rc = dev_alloc((void**) &indeg, (size_t) m * 4, s)) || (rc = dev_alloc((void**) &adj_ptr, (size_t) (m + 1) * 4, s)) ||
-      (rc = dev_alloc((void**) &cursor, (size_t) m * 4, s)) ||
-      (rc = dev_alloc((void**) &adj, (size_t) (nnz > 0 ? nnz : 1) * 4, s)) ||
-      (rc = dev_alloc((void**) &state, 8 * 4, s)) ||
-      (rc = dev_alloc((void**) &partials, (size_t) (cdiv(m, 2048) + 1) * sizeof(long long), s)) ||
-      (rc = dev_alloc((void**) &level_ptr, (size_t) (m + 1) * 4, s)) ||
-      (rc = dev_alloc((void**) &pl->order, (size_t) m * 4, s)))
+  if ((rc = temps.alloc(&indeg, (size_t) m * 4)) || (rc = temps.alloc(&adj_ptr, (size_t) (m + 1) * 4)) ||
+      (rc = temps.alloc(&cursor, (size_t) m * 4)) || (rc = temps.alloc(&adj, (size_t) (nnz > 0 ? nnz : 1) * 4)) ||
+      (rc = temps.alloc(&state, 8 * 4)) || (rc = temps.alloc(&partials, (size_t) (cdiv(m, 2048) + 1) * sizeof(long long))) ||
+      (rc = temps.alloc(&level_ptr, (size_t) (m + 1) * 4)) || (rc = dev_alloc((void**) &pl->order, (size_t) m * 4, s)))
     return fail(rc);
   std::vector<int32_t>& lp = pl->h_level_ptr;
   int32_t n_levels = 0;
@@ -799,8 +786,7 @@ int spblas_gfx950_sptrsv_create(spblas_gfx950_handle_t handle, spblas_gfx950_trs
       e = hipMemsetAsync(state, 0, 32, s);
     if (e != hipSuccess)
       return fail(hip_fail(e));
-    const int cus = handle->num_cus > 0 ? handle->num_cus : 256;
-    const int grid = (int) std::min<int64_t>((int64_t) cus * 8, cdiv(m, 256));
+    const int grid = (int) std::min<int64_t>((int64_t) cu_count(handle) * 8, cdiv(m, 256));
     hipLaunchKernelGGL(trsv_levels_poll_kernel, dim3((unsigned) grid), dim3(256), 0, s, m, rowptr, colind, upper, indeg,
                        state, state + 4, env_int("SPBLAS_GFX950_TRSV_SPIN_LIMIT", 1 << 22));
     hipLaunchKernelGGL(trsv_level_hist_kernel, dim3((unsigned) std::min<int64_t>(1024, cdiv(m, 256))), dim3(256), 0, s, m,
@@ -883,8 +869,7 @@ int spblas_gfx950_sptrsv_create(spblas_gfx950_handle_t handle, spblas_gfx950_trs
       (e = hipStreamSynchronize(s)) != hipSuccess)
     return fail(hip_fail(e));
   }  // Kahn fallback
-  pl->level_ptr = level_ptr;
-  level_ptr = nullptr;
+  pl->level_ptr = temps.release(level_ptr);
   // launch groups of the solve: every level of >= `narrow` rows is a group of its own (one grid-wide step), a run of
   // narrower levels ONE single-workgroup group
   const int narrow = env_int("SPBLAS_GFX950_TRSV_NARROW", 128);
@@ -918,12 +903,6 @@ int spblas_gfx950_sptrsv_create(spblas_gfx950_handle_t handle, spblas_gfx950_trs
     pl->coop_ok = coop_attr != 0 && env_int("SPBLAS_GFX950_TRSV_COOP", intercepted ? 0 : 1) != 0 &&
                   longest_run <= env_int("SPBLAS_GFX950_TRSV_COOP_MAX_RUN", 4096);
   }
-  dev_free(indeg, s);
-  dev_free(adj_ptr, s);
-  dev_free(cursor, s);
-  dev_free(adj, s);
-  dev_free(state, s);
-  dev_free(partials, s);
   return SPBLAS_GFX950_STATUS_SUCCESS;
 }
 

@@ -8,7 +8,7 @@
 // the exact solve pays one store -> load hand-off per level, a sweep pays one pass over the triangle.  A row of level l reads
 // rows of lower levels only, so it holds the exact solve's value from sweep l on: s >= levels - 1 IS the solve.
 //
-// Kernel: a group of G lanes owns a row (G as sptrsv_create picks it from nnz / m), strides its entries, masks them with
+// Kernel: a group of G lanes owns a row (G = lanes_per_row(m, nnz), as in sptrsv_create), strides its entries, masks them with
 // trsv_strict and the column range, carries the diagonal VALUE with its position through the reduction (trsv_row's
 // arithmetic, in trsv_row's order: the bits depend on G alone, not on the grid or on a plan) and lane 0 stores.  The two
 // iterates live in different buffers and a sweep ends at a kernel boundary: plain loads, plain stores, no agent-scope
@@ -24,6 +24,7 @@
 // l - 1 from the other buffer.
 #include "common.hpp"
 #include "complex_api.hpp"
+#include "csr_inspect.hpp"
 #include "lowp_api.hpp"
 #include "trsv_plan.hpp"
 
@@ -133,7 +134,7 @@ static int trsv_sweeps_typed(spblas_gfx950_handle_t h, const spblas_gfx950_trsv_
                              const int32_t* rowptr, const int32_t* colind, const T* values, T alpha, const T* b, T* x,
                              T* work) {
   constexpr int rows_per_block = TRSV_SWEEP_THREADS / G;
-  const int64_t grid_cap = (int64_t) (h->num_cus > 0 ? h->num_cus : 256) * TRSV_SWEEP_BLOCKS_PER_CU;
+  const int64_t grid_cap = (int64_t) cu_count(h) * TRSV_SWEEP_BLOCKS_PER_CU;
   if (pl) {  // rows of level <= s are final after s sweeps: more sweeps than levels - 1 change nothing
     const int last = (int) pl->h_level_ptr.size() - 2;
     if (sweeps > last)
@@ -171,12 +172,9 @@ static int trsv_sweeps_lanes(spblas_gfx950_handle_t h, const spblas_gfx950_trsv_
   const T* bb = static_cast<const T*>(b);
   T* xx = static_cast<T*>(x);
   T* ww = static_cast<T*>(work);
-  switch (lanes) {
-    case 4: return trsv_sweeps_typed<T, 4>(h, pl, m, sweeps, upper, unit, rowptr, colind, v, a, bb, xx, ww);
-    case 16: return trsv_sweeps_typed<T, 16>(h, pl, m, sweeps, upper, unit, rowptr, colind, v, a, bb, xx, ww);
-    case 64: return trsv_sweeps_typed<T, 64>(h, pl, m, sweeps, upper, unit, rowptr, colind, v, a, bb, xx, ww);
-    default: return trsv_sweeps_typed<T, 8>(h, pl, m, sweeps, upper, unit, rowptr, colind, v, a, bb, xx, ww);
-  }
+  return with_lanes(lanes, [&](auto g) {
+    return trsv_sweeps_typed<T, decltype(g)::value>(h, pl, m, sweeps, upper, unit, rowptr, colind, v, a, bb, xx, ww);
+  });
 }
 
 } // namespace spb
@@ -207,9 +205,7 @@ int spblas_gfx950_sptrsv_sweeps(spblas_gfx950_handle_t handle, spblas_gfx950_trs
     return SPBLAS_GFX950_STATUS_INVALID_VALUE;
   if (m == 0)
     return SPBLAS_GFX950_STATUS_SUCCESS;
-  // the rule of sptrsv_create: with and without a plan the same lanes per row, hence the same bits
-  const double avg = (double) nnz / (double) m;
-  const int lanes = avg > 96 ? 64 : (avg > 24 ? 16 : (avg > 6 ? 8 : 4));
+  const int lanes = lanes_per_row(m, nnz);  // sptrsv_create's call: with and without a plan the same lanes, hence the same bits
   const int upper = uplo == SPBLAS_GFX950_UPPER, unit = diag == SPBLAS_GFX950_DIAG_UNIT;
   if (value_type == SPBLAS_GFX950_F32)
     return trsv_sweeps_lanes<float>(handle, plan, lanes, (int) m, sweeps, upper, unit, rowptr, colind, values, alpha, b, x, work);

@@ -16,6 +16,7 @@
 
 #include "common.hpp"
 #include "complex_api.hpp"
+#include "csr_inspect.hpp"
 #include "lowp_api.hpp"
 #include "scan.hpp"
 
@@ -514,10 +515,7 @@ extern "C" int spblas_gfx950_narrow_indices(spblas_gfx950_handle_t handle, int64
   int h_bad = 0;
   hipError_t e = hipMemsetAsync(bad, 0, sizeof(int), s);
   if (e == hipSuccess) {
-    int64_t blocks = cdiv(count, 1024);
-    const int64_t cap = (int64_t) (handle->num_cus > 0 ? handle->num_cus : 256) * 16;
-    blocks = blocks > cap ? cap : blocks;
-    hipLaunchKernelGGL(spt_narrow_kernel, dim3((unsigned) blocks), dim3(256), 0, s, count, src, dst, bound, bad);
+    hipLaunchKernelGGL(spt_narrow_kernel, dim3(stride_grid(handle, cdiv(count, 4))), dim3(256), 0, s, count, src, dst, bound, bad);
     e = hipMemcpyAsync(&h_bad, bad, sizeof(int), hipMemcpyDeviceToHost, s);
   }
   if (e == hipSuccess)
@@ -543,6 +541,7 @@ extern "C" int spblas_gfx950_scale(spblas_gfx950_handle_t handle, int64_t n, con
   if (n == 0)
     return SPBLAS_GFX950_STATUS_SUCCESS;
   const int64_t per = value_type == SPBLAS_GFX950_F32 ? 4 : 2;
+  // (written out, not stride_grid: tests/ladder_tt.py reads the cap and the block of the scale ladder from these lines)
   int64_t blocks = cdiv(cdiv(n, per), 256);
   const int64_t cap = (int64_t) (handle->num_cus > 0 ? handle->num_cus : 256) * 16;
   if (blocks > cap)

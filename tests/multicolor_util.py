@@ -9,8 +9,7 @@ import numpy as np
 import scipy.sparse as sps
 
 import ilu_util as U
-
-LANE_LIMITS = (6, 24, 96)  # nnz / m above which a vertex gets 8 / 16 / 64 lanes (the rule of spblas_gfx950_sptrsv_create)
+import ladder_tt as TT
 
 
 # ===================================================================================================================== key
@@ -28,8 +27,8 @@ def keys(m):
 
 
 def lanes_for(rowptr, colind):
-    avg = colind.size / max(1, rowptr.size - 1)
-    return 64 if avg > 96 else 16 if avg > 24 else 8 if avg > 6 else 4
+    """Lanes per vertex: the library's one rule, spb::lanes_per_row, as tests/ladder_tt.py reads it from csrc/sptrsv.hip."""
+    return TT.lanes_of(colind.size, rowptr.size - 1)
 
 
 # ============================================================================================================== generators

@@ -261,7 +261,7 @@ def test_python_layer_refusals_on_the_device(gpu):
     # a view over other structure arrays with its own inspect result works, and replaces a stale plan in the info
     d2 = Dev(f.rowptr, f.colind, f.values, np.float32)
     sp.ilu0_sweeps(info, d2.a, d2.view(d2.buffer()), d2.buffer(), 2)
-    assert info.state_.key == api._ilu0_key(d2.a)
+    assert info.state_.key == api._structure_key(d2.a)
 
 
 # ---- 6. degenerate shapes -----------------------------------------------------------------------------------------------------------

@@ -94,8 +94,15 @@ def test_dyadic_systems_hold_their_claims_and_are_exact_in_any_order(name, make)
 def test_lane_classes_cover_every_step_of_the_plan_rule():
     assert sorted({make().lanes for _, make in DYADIC}) == list(LANES)
     assert [s[0] for s in TT.trsv_limits()["lane_steps"]] == [6, 24, 96]
-    src = open(os.path.join(TT.CSRC, "sptrsv_sweeps.hip")).read()
-    assert "avg > 96 ? 64 : (avg > 24 ? 16 : (avg > 6 ? 8 : 4))" in src, "the plan-free rule must be sptrsv_create's"
+    # the rule is written once under csrc/ -- lanes_per_row, defined in sptrsv.hip (where TT.trsv_limits reads it) and declared
+    # in the shared header --, and the plans and the plan-free sweeps all call it
+    rule = "avg > 96 ? 64 : (avg > 24 ? 16 : (avg > 6 ? 8 : 4))"
+    srcs = {f: open(os.path.join(TT.CSRC, f)).read() for f in sorted(os.listdir(TT.CSRC)) if f.endswith((".hip", ".hpp"))}
+    assert {f: s.count("avg > 96") for f, s in srcs.items() if "avg > 96" in s} == {"sptrsv.hip": 1}
+    assert srcs["sptrsv.hip"].count(rule) == 1 and "int lanes_per_row(int64_t m, int64_t nnz);" in srcs["csr_inspect.hpp"]
+    assert "pl->lanes = lanes_per_row(m, nnz);" in srcs["sptrsv.hip"]
+    for f in ("sptrsv_sweeps.hip", "multicolor.hip", "gauss_seidel.hip"):
+        assert "lanes_per_row(" in srcs[f] and "avg > 96" not in srcs[f], f
 
 
 def _dominant(kind):
