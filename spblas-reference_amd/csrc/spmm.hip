@@ -26,6 +26,7 @@
 #include "common.hpp"
 #include "complex_api.hpp"
 #include "lowp_api.hpp"
+#include "multiply_args.hpp"
 #include "plan.hpp"
 #include "scan.hpp"
 
@@ -1294,10 +1295,9 @@ extern "C" int spblas_gfx950_spmm(spblas_gfx950_handle_t handle, spblas_gfx950_p
   if ((offset_type != SPBLAS_GFX950_I32 && offset_type != SPBLAS_GFX950_I64) ||
       (value_type != SPBLAS_GFX950_F32 && value_type != SPBLAS_GFX950_F64))
     return SPBLAS_GFX950_STATUS_INVALID_VALUE;
-  if (!alpha || !beta || !rowptr || (nnz > 0 && (!colind || !values || !B)) || (m > 0 && n > 0 && !C))
+  if (!alpha || !beta || !csr_arrays_ok(nnz, rowptr, colind, values) || (nnz > 0 && !B) || (m > 0 && n > 0 && !C))
     return SPBLAS_GFX950_STATUS_INVALID_POINTER;
-  if (plan && (plan->m != m || plan->n != k || plan->nnz != nnz || plan->rowptr != rowptr ||
-               plan->colind != colind || plan->offset_type != offset_type || plan->value_type != value_type))
+  if (plan && !plan_matches(*plan, m, k, nnz, rowptr, colind, offset_type, value_type))
     return SPBLAS_GFX950_STATUS_PLAN_MISMATCH;
   if (plan) {  // the long-row partials are the plan's
     plan->last_stream = handle->stream;
@@ -1325,9 +1325,8 @@ extern "C" int spblas_gfx950_spmm_strided(spblas_gfx950_handle_t handle, spblas_
     return lowp_spmm_strided(handle, plan, m, k, n, nnz, alpha, rowptr, colind, values, B, brs, bcs, beta, C, crs, ccs,
                              offset_type, value_type);
   if (bcs == 1 && ccs == 1) {  // both layout_right: the regular kernels, plan included
-    // (a layout_left mdspan with ONE row also has strides (1, 1): its row stride says nothing -- an operand of at most one
-    // row gets the leading dimension the regular entry point asks for; round-4 advisor finding)
-    const int64_t ldb = k <= 1 ? (n > 1 ? n : 1) : brs, ldc = m <= 1 ? (n > 1 ? n : 1) : crs;
+    // (an operand of at most one row gets the leading dimension the regular entry point asks for: one_row_ld)
+    const int64_t ldb = one_row_ld(k, n, brs), ldc = one_row_ld(m, n, crs);
     return spblas_gfx950_spmm(handle, plan, m, k, n, nnz, alpha, rowptr, colind, values, B, ldb, beta, C, ldc, offset_type,
                               value_type);
   }
@@ -1336,20 +1335,16 @@ extern "C" int spblas_gfx950_spmm_strided(spblas_gfx950_handle_t handle, spblas_
   if (m < 0 || k < 0 || n < 0 || nnz < 0 || m > INT32_MAX || k > INT32_MAX)
     return SPBLAS_GFX950_STATUS_INVALID_SIZE;
   // each operand is layout_right (column stride 1, rows >= n apart) or layout_left (row stride 1, columns >= rows apart)
-  const auto layout_ok = [n](int64_t rows, int64_t rs, int64_t cs) {
-    return (cs == 1 && rs >= n) || (rs == 1 && cs >= rows) || rows <= 1 || n <= 1;
-  };
-  if (brs < 0 || bcs < 0 || crs < 0 || ccs < 0 || !layout_ok(k, brs, bcs) || !layout_ok(m, crs, ccs))
+  if (!spmm_strides_ok(m, k, n, brs, bcs, crs, ccs))
     return SPBLAS_GFX950_STATUS_INVALID_SIZE;
   if (offset_type == SPBLAS_GFX950_I32 && nnz > INT32_MAX)
     return SPBLAS_GFX950_STATUS_INVALID_SIZE;
   if ((offset_type != SPBLAS_GFX950_I32 && offset_type != SPBLAS_GFX950_I64) ||
       (value_type != SPBLAS_GFX950_F32 && value_type != SPBLAS_GFX950_F64))
     return SPBLAS_GFX950_STATUS_INVALID_VALUE;
-  if (!alpha || !beta || !rowptr || (nnz > 0 && (!colind || !values || !B)) || (m > 0 && n > 0 && !C))
+  if (!alpha || !beta || !csr_arrays_ok(nnz, rowptr, colind, values) || (nnz > 0 && !B) || (m > 0 && n > 0 && !C))
     return SPBLAS_GFX950_STATUS_INVALID_POINTER;
-  if (plan && (plan->m != m || plan->n != k || plan->nnz != nnz || plan->rowptr != rowptr ||
-               plan->colind != colind || plan->offset_type != offset_type || plan->value_type != value_type))
+  if (plan && !plan_matches(*plan, m, k, nnz, rowptr, colind, offset_type, value_type))
     return SPBLAS_GFX950_STATUS_PLAN_MISMATCH;
   if (value_type == SPBLAS_GFX950_F32)
     return offset_type == SPBLAS_GFX950_I32

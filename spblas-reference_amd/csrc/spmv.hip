@@ -17,6 +17,7 @@
 #include "common.hpp"
 #include "complex_api.hpp"
 #include "lowp_api.hpp"
+#include "multiply_args.hpp"
 #include "plan.hpp"
 #include "scan.hpp"
 
@@ -702,7 +703,8 @@ static void launch_vector(hipStream_t s, int64_t m, const O* rowptr, const int32
                      colind, values, x, y, alpha, beta);
 }
 
-static int pick_lpr(int64_t m, int64_t nnz) {
+// The lanes-per-row rule of the vector kernels of every value type (declared in multiply_args.hpp): the ONLY place it is written.
+int pick_lpr(int64_t m, int64_t nnz) {
   const double avg = m > 0 ? (double) nnz / (double) m : 0.0;
   int lpr = 2;
   while (lpr < 64 && (double) lpr * 1.5 < avg)
@@ -1698,7 +1700,7 @@ int spblas_gfx950_spmv(spblas_gfx950_handle_t handle, spblas_gfx950_plan_t plan,
     return SPBLAS_GFX950_STATUS_INVALID_VALUE;
   const int64_t ylen = op == SPBLAS_GFX950_OP_N ? m : n, xlen = op == SPBLAS_GFX950_OP_N ? n : m;
   const bool detached = plan && plan->detached;  // (spblas_gfx950_spmv_plan_detach: the multiply takes no matrix arrays)
-  if (!alpha || !beta || (!detached && (!rowptr || (nnz > 0 && (!colind || !values)))) || (ylen > 0 && !y) ||
+  if (!alpha || !beta || (!detached && !csr_arrays_ok(nnz, rowptr, colind, values)) || (ylen > 0 && !y) ||
       (xlen > 0 && nnz > 0 && !x))
     return SPBLAS_GFX950_STATUS_INVALID_POINTER;
   if (detached) {
@@ -1707,8 +1709,7 @@ int spblas_gfx950_spmv(spblas_gfx950_handle_t handle, spblas_gfx950_plan_t plan,
     if (op != SPBLAS_GFX950_OP_N)
       return SPBLAS_GFX950_STATUS_INVALID_VALUE;
   } else if (plan) {
-    if (plan->m != m || plan->n != n || plan->nnz != nnz || plan->rowptr != rowptr ||
-        plan->colind != colind || plan->offset_type != offset_type || plan->value_type != value_type)
+    if (!plan_matches(*plan, m, n, nnz, rowptr, colind, offset_type, value_type))
       return SPBLAS_GFX950_STATUS_PLAN_MISMATCH;
     if (op != SPBLAS_GFX950_OP_N)
       plan = nullptr;  // plans describe op = N only

@@ -93,8 +93,8 @@ def spmm_parts_rule():
 
 
 def lanes_per_row_steps():
-    """pick_lpr of spmv.hip / complex.hip / lowp.hip: lanes per row double from 2 to the wave while 1.5 * lanes < the mean row
-    length; the row-block kernels' phase 2 doubles from 1.  Every step is a power of two up to 64."""
+    """pick_lpr of spmv.hip (the one rule of every value type's vector kernels): lanes per row double from 2 to the wave while
+    1.5 * lanes < the mean row length; the row-block kernels' phase 2 doubles from 1.  Every step is a power of two up to 64."""
     return [1 << k for k in range(7)]
 
 
