@@ -272,6 +272,26 @@ int spblas_gfx950_spmv(spblas_gfx950_handle_t handle, spblas_gfx950_plan_t plan,
                        const int32_t* colind, const void* values, const void* x, const void* beta,
                        void* y, int offset_type, int value_type);
 
+/* Diagnostic, like plan_info: what the last spblas_gfx950_spmv with op == OP_T and no plan (real value types) did on this
+ * handle.  Writes min(n_out, 8) entries: out[0] = path (SPMV_T_NONE before the first such call, SPMV_T_SCATTER: one atomic per
+ * entry, SPMV_T_TWO_PASS: through the workspace); [1] = why the scatter kernel ran (SPMV_T_NOT_WANTED: below the size rule or
+ * SPBLAS_GFX950_SPMV_T2=0, SPMV_T_DOES_NOT_FIT: more than 1 024 slices, no entries, or a count beyond 32 bits,
+ * SPMV_T_CAPTURING: the stream is recording a graph, SPMV_T_NO_SCRATCH: the handle's scratch could not be sized; 0 for the
+ * two-pass form); [2] = slice width W in columns, [3] = slices S, [4] = tiles of 8 192 entries -- the geometry the decision
+ * was made on, reported for both paths --; [5] = segment length in entries (0 unless the two-pass form was wanted and fits);
+ * [6] = 1 if a SPBLAS_GFX950_SPMV_T2_W test hook was set but ignored (below 64 or wider than the LDS holds); [7] = work items
+ * of the accumulate pass, or -1 (scatter path, another call has taken the handle's scratch since, or the stream is
+ * capturing).  [0] .. [6] are host integers; asking for [7] (n_out > 7) after a two-pass call copies one word back and
+ * SYNCHRONISES the stream of that call.  Changes nothing about the multiply. */
+#define SPBLAS_GFX950_SPMV_T_NONE 0
+#define SPBLAS_GFX950_SPMV_T_SCATTER 1
+#define SPBLAS_GFX950_SPMV_T_TWO_PASS 2
+#define SPBLAS_GFX950_SPMV_T_NOT_WANTED 1
+#define SPBLAS_GFX950_SPMV_T_DOES_NOT_FIT 2
+#define SPBLAS_GFX950_SPMV_T_CAPTURING 3
+#define SPBLAS_GFX950_SPMV_T_NO_SCRATCH 4
+int spblas_gfx950_spmv_t_last(spblas_gfx950_handle_t handle, int64_t* out, int n_out);
+
 /* Conjugated operands (complex types only): y = alpha * op'(A) * x' + beta * y with bit 0 of conj_flags = conj(A) (every stored
  * value conjugated) and bit 1 = conj(x).  conj_flags = 0 is spblas_gfx950_spmv itself; non-zero flags with a real value type
  * or bits above 1 return STATUS_INVALID_VALUE.  Complex values take op = N only (STATUS_NOT_SUPPORTED for op = T).  Products

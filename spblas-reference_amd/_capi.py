@@ -32,6 +32,8 @@ LOWER, UPPER = 0, 1
 DIAG_EXPLICIT, DIAG_UNIT = 0, 1
 GS_FORWARD, GS_BACKWARD, GS_SYMMETRIC = 0, 1, 2
 SPMV_AUTO, SPMV_VECTOR, SPMV_ROWBLOCK, SPMV_SLICED = 0, 1, 2, 3
+SPMV_T_NONE, SPMV_T_SCATTER, SPMV_T_TWO_PASS = 0, 1, 2                                       # spmv_t_last: out[0]
+SPMV_T_NOT_WANTED, SPMV_T_DOES_NOT_FIT, SPMV_T_CAPTURING, SPMV_T_NO_SCRATCH = 1, 2, 3, 4    # ... and out[1]
 OPT_BIN_ROW_ALIGN = 1
 OPT_MAX_KSPLIT = 2
 OPT_VALUE_SNAPSHOT = 3
@@ -61,6 +63,7 @@ PROTOTYPES = [
     ("spblas_gfx950_spmv", c_int,
      [c_void_p, c_void_p, c_int, c_i64, c_i64, c_i64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
       c_void_p, c_int, c_int]),
+    ("spblas_gfx950_spmv_t_last", c_int, [c_void_p, ctypes.POINTER(c_i64), c_int]),
     ("spblas_gfx950_spmm", c_int,
      [c_void_p, c_void_p, c_i64, c_i64, c_i64, c_i64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_i64,
       c_void_p, c_void_p, c_i64, c_int, c_int]),

@@ -262,6 +262,20 @@ class _Handle:
     def set_option(self, option, value):
         check(_capi.lib().spblas_gfx950_set_option(self.h, option, value), "spblas_gfx950_set_option")
 
+    def spmv_t_last(self, with_items=True):
+        """What the last un-inspected transposed multiply on this handle did (spblas_gfx950_spmv_t_last; a diagnostic, like
+        _Plan.info): path 'none' / 'scatter' / 'two_pass', why the scatter kernel ran, the slice width W, the slices S, the
+        tiles and the segment length the decision was made on.  with_items also copies the number of work items of the
+        accumulate pass back, which SYNCHRONISES the stream of that call (-1 where there is none to report)."""
+        arr = (ctypes.c_int64 * 8)()
+        check(_capi.lib().spblas_gfx950_spmv_t_last(self.h, arr, 8 if with_items else 7), "spblas_gfx950_spmv_t_last")
+        out = {"path": ("none", "scatter", "two_pass")[arr[0]],
+               "why": (None, "not_wanted", "does_not_fit", "capturing", "no_scratch")[arr[1]],
+               "W": arr[2], "S": arr[3], "ntile": arr[4], "seg": arr[5], "w_hook_ignored": arr[6]}
+        if with_items:
+            out["n_items"] = arr[7]
+        return out
+
     @classmethod
     def current(cls, device):
         if device.type != "cuda":

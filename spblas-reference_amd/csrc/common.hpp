@@ -56,6 +56,16 @@ struct spblas_gfx950_handle_s {
   void* scratch = nullptr;
   size_t scratch_bytes = 0;
   hipStream_t scratch_stream = nullptr;
+  uint64_t scratch_epoch = 0;  // handle_scratch calls so far: what points into the scratch is good for one epoch
+  // what the last un-inspected transposed multiply on this handle did (spblas_gfx950_spmv_t_last: a diagnostic for tests).
+  // Host integers written by spmv_typed next to its decision; n_items points into the scratch of `epoch`.
+  struct spmv_t_last_t {
+    int path = 0, why = 0, w_hook_ignored = 0;  // SPBLAS_GFX950_SPMV_T_* of spblas_gfx950.h
+    int64_t W = 0, S = 0, ntile = 0, seg = 0;
+    const int* n_items = nullptr;
+    uint64_t epoch = 0;
+    hipStream_t stream = nullptr;
+  } spmv_t_last;
   // pinned, device-visible host buffer for small read-backs (spb::readback_*), and the copies staged in it
   void* pinned = nullptr;
   size_t pinned_bytes = 0, pinned_used = 0;
@@ -151,6 +161,7 @@ inline int handle_scratch(spblas_gfx950_handle_s* h, size_t bytes, void** out) {
     h->scratch_bytes = bytes;
   }
   h->scratch_stream = h->stream;
+  ++h->scratch_epoch;
   *out = h->scratch;
   return SPBLAS_GFX950_STATUS_SUCCESS;
 }

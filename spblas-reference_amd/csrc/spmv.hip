@@ -787,6 +787,7 @@ static int spmv_typed(spblas_gfx950_handle_t h, spblas_gfx950_plan_s* pl, int op
     // slice width: as many slices as the accumulate pass has workgroup slots (two per CU: ONE round of work items -- 611 slices
     // of 16 384 columns on 512 slots were two rounds, 0.236 against 0.170 ms), a multiple of 64, an LDS-resident slice of y of
     // at most 76 KiB (two workgroups per CU), 16-bit local columns, at most T2_SMAX slices
+    bool w_ignored = false;  // (a _T2_W hook outside 64 .. Wcap: reported by spblas_gfx950_spmv_t_last)
     int64_t Wsl = (cdiv(n, (int64_t) 2 * cus) + 63) & ~(int64_t) 63;
     const int64_t Wcap = (76 * 1024) / (int64_t) sizeof(T);
     Wsl = Wsl < 4096 ? 4096 : Wsl > Wcap ? Wcap : Wsl;
@@ -796,12 +797,20 @@ static int spmv_typed(spblas_gfx950_handle_t h, spblas_gfx950_plan_s* pl, int op
       const int w_env = env_int_spmv("SPBLAS_GFX950_SPMV_T2_W", 0);
       if (w_env >= 64 && w_env <= Wcap)
         Wsl = w_env & ~63;
+      else
+        w_ignored = w_env != 0;
     }
     const unsigned wrec = (unsigned) (((uint64_t) 1 << 32) / (uint64_t) Wsl);
     const int64_t Ssl = cdiv(n, Wsl), ntile = cdiv(nnz, T2_TILE);
     const bool t2_fits = m > 0 && nnz > 0 && nnz < INT32_MAX - T2_TILE && Ssl <= T2_SMAX && ntile < INT32_MAX &&
                          Ssl * ntile < INT32_MAX;
     const bool t2_want = t2_env == 1 || (t2_env != 0 && nnz >= ((int64_t) 4 << 20) && n >= 65536);
+    auto& last = h->spmv_t_last;  // the decision, for spblas_gfx950_spmv_t_last
+    last = {};
+    last.path = SPBLAS_GFX950_SPMV_T_SCATTER;
+    last.why = !t2_want ? SPBLAS_GFX950_SPMV_T_NOT_WANTED : SPBLAS_GFX950_SPMV_T_DOES_NOT_FIT;
+    last.w_hook_ignored = w_ignored ? 1 : 0;
+    last.W = Wsl, last.S = Ssl, last.ntile = ntile;
     if (t2_fits && t2_want) {
       const int64_t nscan = Ssl * ntile, nblk = cdiv(nscan, 2048);  // counts[slice][tile] + the total; the scan's block sums
       const size_t off_cnt = 0, off_part = (off_cnt + (size_t) (nscan + 1) * 4 + 255) & ~(size_t) 255,
@@ -816,9 +825,12 @@ static int spmv_typed(spblas_gfx950_handle_t h, spblas_gfx950_plan_s* pl, int op
       const size_t off_lcol = (off_prod + (size_t) nnz * sizeof(T) + 255) & ~(size_t) 255;
       const size_t bytes = off_lcol + (size_t) nnz * 2 + 256;
       void* ws = nullptr;
+      last.seg = seg;
       // (never inside a stream capture: the recorded launches would keep pointers into the handle's scratch, which a later call
       // may grow, i.e. free and allocate again -- a captured un-inspected transposed multiply keeps the scatter kernel)
-      if (!stream_capturing(s) && handle_scratch(h, bytes, &ws) == SPBLAS_GFX950_STATUS_SUCCESS) {
+      const bool capturing = stream_capturing(s);
+      last.why = capturing ? SPBLAS_GFX950_SPMV_T_CAPTURING : SPBLAS_GFX950_SPMV_T_NO_SCRATCH;
+      if (!capturing && handle_scratch(h, bytes, &ws) == SPBLAS_GFX950_STATUS_SUCCESS) {
         char* w8 = static_cast<char*>(ws);
         int32_t* counts = reinterpret_cast<int32_t*>(w8 + off_cnt);
         long long* partials = reinterpret_cast<long long*>(w8 + off_part);
@@ -827,6 +839,8 @@ static int spmv_typed(spblas_gfx950_handle_t h, spblas_gfx950_plan_s* pl, int op
         int4* items = reinterpret_cast<int4*>(w8 + off_items);
         T* prod = reinterpret_cast<T*>(w8 + off_prod);
         uint16_t* lcol = reinterpret_cast<uint16_t*>(w8 + off_lcol);
+        last.path = SPBLAS_GFX950_SPMV_T_TWO_PASS, last.why = 0;
+        last.n_items = n_items, last.epoch = h->scratch_epoch, last.stream = s;
         hipLaunchKernelGGL((plan_window_rows_kernel<O>), dim3((unsigned) cdiv(ntile + 1, 256)), dim3(256), 0, s, m, ntile, T2_TILE,
                            rowptr, tile_row);
         hipLaunchKernelGGL(t2_hist_kernel, dim3((unsigned) ntile), dim3(256), 0, s, nnz, colind, (int) Wsl, wrec, (int) Ssl, ntile,
@@ -1635,6 +1649,28 @@ int spblas_gfx950_plan_info(spblas_gfx950_plan_t plan, int64_t info[12]) {
   info[9] = tp->bin_aligned;
   info[10] = tp->n_xitems;
   info[11] = tp->n_ritems;
+  return SPBLAS_GFX950_STATUS_SUCCESS;
+}
+
+int spblas_gfx950_spmv_t_last(spblas_gfx950_handle_t handle, int64_t* out, int n_out) {
+  if (!handle)
+    return SPBLAS_GFX950_STATUS_INVALID_HANDLE;
+  if (!out)
+    return SPBLAS_GFX950_STATUS_INVALID_POINTER;
+  if (n_out < 1)
+    return SPBLAS_GFX950_STATUS_INVALID_SIZE;
+  const auto& last = handle->spmv_t_last;
+  int64_t v[8] = {last.path, last.why, last.W, last.S, last.ntile, last.seg, last.w_hook_ignored, -1};
+  // the number of work items lies in the handle's scratch: still there while no later call has taken the scratch
+  if (n_out > 7 && last.path == SPBLAS_GFX950_SPMV_T_TWO_PASS && last.n_items && last.epoch == handle->scratch_epoch &&
+      !stream_capturing(last.stream)) {
+    int n_items = -1;
+    SPB_HIP(hipMemcpyAsync(&n_items, last.n_items, sizeof(int), hipMemcpyDeviceToHost, last.stream));
+    SPB_HIP(hipStreamSynchronize(last.stream));
+    v[7] = n_items;
+  }
+  for (int i = 0; i < n_out && i < 8; ++i)
+    out[i] = v[i];
   return SPBLAS_GFX950_STATUS_SUCCESS;
 }
 

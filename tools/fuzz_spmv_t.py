@@ -4,7 +4,11 @@ slot: vendor/rocsparse/detail/get_transpose.hpp:19-29) against the CPU oracle (r
 Three forms per case: the un-inspected call through the C ABI in its two-pass form (forced for any size, with random slice
 widths and segment lengths: SPBLAS_GFX950_SPMV_T2=1, _T2_W, _T2_SEG), the scatter kernel (=0), and the inspected csc_view
 operand of the host layer (device transpose at inspect, the CSR plans on the copy, arrays handed back where the plan is
-self-contained)."""
+self-contained).
+Random columns and row lengths almost never land on a tile, slice or segment edge, and this tool cannot tell which path a call
+took (a slice width the LDS cannot hold -- fp32's 19392 in fp64 -- is ignored without a word): the deterministic counterpart is the ladder in tests/ladder_t2.py
+(tests/test_gpu_t2_ladders.py in the suite), which parks a case on every such edge and asserts the path and geometry through
+spblas_gfx950_spmv_t_last before it looks at y."""
 import ctypes, os, sys
 import numpy as np, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
