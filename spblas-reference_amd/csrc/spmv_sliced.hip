@@ -19,7 +19,8 @@
 //   expand  x slice -> LDS; flat pass over the slice's contiguous blocks of A':
 //           P[blkdst[blk]] = s_val[blk] * xs[s_col[blk]]   -- linear 16-byte reads, and writes that are
 //           linear inside every 128-byte block (a block-permuted stream: tools/ubench/hbm_pieces.hip shows
-//           it runs within 3-5 % of the fully linear copy as long as whole lines are written)
+//           it runs within 3-5 % of the fully linear copy as long as whole lines are written); blkdst[] and blksrc[]
+//           (where a block's entries start in the compact A') with plain cached loads, A' itself non-temporally
 //   reduce  one wavefront per wave-bin: H accumulators in LDS; the bin's part of P and s_row is ONE
 //           contiguous stream, read with 16-byte / 8-byte lane accesses (4 entries per lane, no run
 //           descriptors, no line over-fetch);  y = alpha*acc + beta*y
@@ -44,6 +45,7 @@
 #include <vector>
 
 #include "common.hpp"
+#include "expand_map.hpp"
 #include "plan.hpp"
 #include "scan.hpp"
 
@@ -1238,8 +1240,11 @@ typedef unsigned short u16x4 __attribute__((ext_vector_type(4)));
 
 // expand: P[blkdst[blk]] = s_val[blk] * x[slice_base + s_col[blk]] over the slice's contiguous blocks of A'.
 // The x slice lives in LDS.  Eight consecutive lanes own one block of 32 entries (4 entries = 16 B of values,
-// 8 B of columns each): the wavefront reads 8 consecutive blocks -- 1 KiB of values -- and stores 8 whole
-// 128-byte lines of products, each at the place the reduce kernel's stream wants it.
+// 8 B of columns each): a load instruction of the wavefront reads 8 consecutive blocks -- 1 KiB of values -- and it stores
+// 8 whole 128-byte lines of products, each at the place the reduce kernel's stream wants it.  A thread keeps two blocks in
+// flight; the wavefront's two windows and the windows of the 16 wavefronts lie side by side (expand_map.hpp), so that an
+// iteration of the workgroup requests ONE contiguous piece of A' and of the block tables while all of it is in flight:
+// a line two windows share is fetched once (profiles/expand_read_attribution.md: 0.771 -> 0.698 GB read at cfg2).
 // NT: the products are stored with the non-temporal hint.  Which flavour is faster depends on the BOX (round 3,
 // tools/exp_r03o.sh, same binaries): where the reduce pays for the expand's write-backs (reduce 118-122 us after plain
 // stores) the hint moves that cost into the expand and the pair gains 1-3 %; where it does not (reduce 105-107 us) the hint
@@ -1269,8 +1274,7 @@ __global__ __launch_bounds__(PB_THREADS) void pb_expand_kernel(int64_t n, int W,
   T* xs = reinterpret_cast<T*>(smem);
   const int tid = threadIdx.x;
   const int sub = (tid & (LPB - 1)) * 4;  // first of this lane's 4 entries inside its block
-  const int bsel = tid / LPB;             // block inside the workgroup's pass of PB_THREADS / LPB blocks
-  constexpr int PASS = PB_THREADS / LPB;
+  static_assert(PB_THREADS == PB_EXP_THREADS, "expand_map.hpp");
   // Chunked multi-GPU step (cw.flags != nullptr): x IS the previous step's y, row-sharded over cw.n_ranks ranks, and the
   // peers deliver their rows chunk by chunk (peer stores + one flag per (rank, chunk) after the chunk's stores).  Before a
   // workgroup loads an x slice it waits for exactly the chunks that slice is made of -- bounded, with s_sleep -- so the
@@ -1379,12 +1383,39 @@ __global__ __launch_bounds__(PB_THREADS) void pb_expand_kernel(int64_t n, int W,
       else
         pack4<T>::store(ptr, val);
     };
-    int blk = b0 + bsel;
+    // The two block tables (8 B per block, 27 MB at cfg2) are read with plain cached loads: the wavefronts that share a
+    // table line run on this CU at the same time, and under the non-temporal policy each of them fetched the line again
+    // (profiles/expand_read_attribution.md: 0.047 GB of the expand's 0.771 GB at cfg2)
+#ifdef PB_EXP_TAB_STREAM  // A/B only (tools/build_variant.sh): the non-temporal table loads of before
+    auto tab_load = [](const int32_t* p) { return stream_load(p); };
+#else
+    auto tab_load = [](const int32_t* p) { return *p; };
+#endif
     // A' is compact (round 3): the entries of block k start at blksrc[k], a multiple of 4; the lanes past the end of a
     // run's last block read the entries that follow it -- their products land on pad positions of P, which the reduce
-    // leaves out (row = H / code 255)
-    for (; blk + PASS < b1; blk += 2 * PASS) {
-      const int ea = stream_load(blksrc + blk) + sub, eb = stream_load(blksrc + blk + PASS) + sub;
+    // leaves out (row = H / code 255).  Which blocks a thread takes in iteration it: expand_map.hpp
+    for (int it = 0;; ++it) {
+      const pb_exp_blocks m = pb_exp_map(tid, it, b0, b1, LPB);
+      if (!m.b_on) {
+        if (m.a_on) {
+          const int ea = tab_load(blksrc + m.a) + sub;
+          T va[4], pa[4];
+          if constexpr (!VF)
+            pack4<T>::load(s_val + ea, va);
+          const u16x4 ca = stream_load(reinterpret_cast<const u16x4*>(s_col + ea));
+          const int da = tab_load(blkdst + m.a);
+#pragma unroll
+          for (int j = 0; j < 4; ++j) {
+            if constexpr (VF)
+              pa[j] = xs[ca[j]];
+            else
+              pa[j] = va[j] * xs[ca[j]];
+          }
+          put(P + (int64_t) da * PB_BLK + sub, pa);
+        }
+        break;
+      }
+      const int ea = tab_load(blksrc + m.a) + sub, eb = tab_load(blksrc + m.b) + sub;
       T va[4], vb[4], pa[4], pb[4];
 #ifdef PB_EXP_PLAIN_A  // A/B only: cached loads of the (now unaligned) A' blocks
       pack4<T>::load_cached(s_val + ea, va);
@@ -1399,7 +1430,7 @@ __global__ __launch_bounds__(PB_THREADS) void pb_expand_kernel(int64_t n, int W,
       const u16x4 ca = stream_load(reinterpret_cast<const u16x4*>(s_col + ea));
       const u16x4 cb = stream_load(reinterpret_cast<const u16x4*>(s_col + eb));
 #endif
-      const int da = stream_load(blkdst + blk), db = stream_load(blkdst + blk + PASS);
+      const int da = tab_load(blkdst + m.a), db = tab_load(blkdst + m.b);
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         if constexpr (VF) {
@@ -1412,22 +1443,6 @@ __global__ __launch_bounds__(PB_THREADS) void pb_expand_kernel(int64_t n, int W,
       }
       put(P + (int64_t) da * PB_BLK + sub, pa);
       put(P + (int64_t) db * PB_BLK + sub, pb);
-    }
-    for (; blk < b1; blk += PASS) {
-      const int ea = stream_load(blksrc + blk) + sub;
-      T va[4], pa[4];
-      if constexpr (!VF)
-        pack4<T>::load(s_val + ea, va);
-      const u16x4 ca = stream_load(reinterpret_cast<const u16x4*>(s_col + ea));
-      const int da = stream_load(blkdst + blk);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        if constexpr (VF)
-          pa[j] = xs[ca[j]];
-        else
-          pa[j] = va[j] * xs[ca[j]];
-      }
-      put(P + (int64_t) da * PB_BLK + sub, pa);
     }
   };
   auto process = [&](int b0, int b1) {
