@@ -382,6 +382,17 @@ int spblas_gfx950_bcast_wait_before(spblas_gfx950_handle_t handle, const void* f
  * [2] entries inside them, [3] long rows. */
 int spblas_gfx950_spmm_inspect(spblas_gfx950_handle_t handle, spblas_gfx950_plan_t plan);
 int spblas_gfx950_spmm_plan_info(spblas_gfx950_plan_t plan, int64_t info[4]);
+/* What spmm_inspect decided, block by block (a diagnostic for tests, like spmv_t_last; no kernel runs).  counts: [0]
+ * inspected, [1] row blocks of 32 rows, [2] qualifying blocks, [3] those on the band path's matrix-core kernel, [4] entries in
+ * the qualifying blocks, [5] band kernels (0: the tile kernel), [6] B rows staged per chunk, [7] wavefronts per workgroup
+ * of the entry-loop kernel, [8] the per-mille window density of the matrix-core rule, [9] entries per tile a block had to
+ * hold.  kind (counts[1] bytes: 0 row-group kernel, 1 entry loop / tile kernel, 2 matrix cores), win (2 per block:
+ * smallest and largest column) and tiles (17 per block: count, then ascending tile ids) are HOST arrays, each may be NULL;
+ * they are copied on the handle's stream, which is synchronised once.  A plan the probe did not run on (not fp32, fewer
+ * than 256 entries, SPBLAS_GFX950_SPMM_NO_PANEL) reports ten zeros and copies nothing.  NOT_SUPPORTED while the stream is
+ * capturing. */
+int spblas_gfx950_spmm_plan_blocks(spblas_gfx950_handle_t handle, spblas_gfx950_plan_t plan, int64_t counts[10],
+                                   unsigned char* kind, int32_t* win, int32_t* tiles);
 int spblas_gfx950_spmm(spblas_gfx950_handle_t handle, spblas_gfx950_plan_t plan, int64_t m, int64_t k,
                        int64_t n, int64_t nnz, const void* alpha, const void* rowptr,
                        const int32_t* colind, const void* values, const void* B, int64_t ldb,

@@ -45,6 +45,7 @@ import ctypes
 import threading
 import weakref
 
+import numpy as np
 import torch
 
 from . import _capi
@@ -406,6 +407,24 @@ class _Plan:
         arr = (ctypes.c_int64 * 4)()
         check(_capi.lib().spblas_gfx950_spmm_plan_info(self.plan, arr), "spblas_gfx950_spmm_plan_info")
         return dict(zip(("inspected", "panel_blocks", "panel_nnz", "long_rows"), list(arr)))
+
+    def spmm_blocks(self):
+        """What the SpMM inspect decided, block by block (spblas_gfx950_spmm_plan_blocks; a diagnostic, like spmm_info):
+        the counts, and per block of 32 rows its kind (0 row-group kernel, 1 entry loop / tile kernel, 2 matrix cores), its
+        column window (nblk x 2) and its tile table (nblk x 17: count, then ascending tile ids) as numpy arrays.
+        SYNCHRONISES the calling thread's stream.  All counts zero and empty arrays for a plan the probe did not run on."""
+        names = ("inspected", "nblk", "npanel", "ndense", "panel_nnz", "band", "band_ch", "band_waves", "band_dense_pm",
+                 "min_per_tile")
+        fn, h = _capi.lib().spblas_gfx950_spmm_plan_blocks, self._calling_handle().h
+        arr = (ctypes.c_int64 * 10)()
+        check(fn(h, self.plan, arr, None, None, None), "spblas_gfx950_spmm_plan_blocks")
+        nblk = int(arr[1])
+        kind, win, tiles = np.zeros(nblk, np.uint8), np.zeros((nblk, 2), np.int32), np.zeros((nblk, 17), np.int32)
+        if nblk:
+            check(fn(h, self.plan, arr, kind.ctypes.data, win.ctypes.data, tiles.ctypes.data), "spblas_gfx950_spmm_plan_blocks")
+        out = dict(zip(names, list(arr)))
+        out.update(kind=kind, win=win, tiles=tiles)
+        return out
 
     def update_values(self, values):
         """Refresh the plan after A's values changed in place (only the SLICED re-tiling keeps

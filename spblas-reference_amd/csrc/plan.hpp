@@ -140,6 +140,7 @@ struct spblas_gfx950_plan_s {
   int mm_band = 1;                       // qualifying blocks go to the band kernels (0: the tile kernel of rounds 3 - 5)
   int mm_band_ch = 128, mm_band_waves = 8;  // B rows staged per chunk, wavefronts per workgroup
   int mm_band_dense_pm = 1001;           // window density (per mille) from which a block's contraction runs on the matrix cores
+  int mm_min_per_tile = 0;               // entries per tile the probe asked for (spblas_gfx950_spmm_plan_blocks)
   void* mm_long_part = nullptr;          // T[n_long * mm_long_parts * n] partial rows of the long rows (grown on demand)
   int64_t mm_long_cap = 0;               // elements held by mm_long_part
   int mm_long_parts = 1;

@@ -248,6 +248,9 @@ static constexpr int MM_KT = 64;      // columns of A / rows of B per tile (32 K
 static constexpr int MM_MAXT = 16;    // tiles per block at most
 static constexpr int MM_NP = 128;     // columns of B / C per pass (4 wavefronts x 32)
 static constexpr int MM_TS = MM_MAXT + 1;  // ints per block in the tile table: count + ids
+static constexpr int MM_LDS_BYTES = 160 * 1024;  // LDS a workgroup can ask for on gfx950
+static constexpr int MM_DENSE_CH = 248;    // most B rows the matrix-core band kernel stages: 124 KiB beside its 32 KiB A tile
+                                           // (4 KiB stay free: that kernel also has static LDS, its block-wide vote)
 
 // inspect: one wavefront per row block.  tiles[b*9] = number of distinct aligned column tiles of the block (9 = more
 // than MM_MAXT), tiles[b*9 + 1 ..] = their ids ascending; is_panel[b] = 1 when the block qualifies: <= MM_MAXT
@@ -1061,9 +1064,10 @@ static int spmm_typed(spblas_gfx950_handle_t h, spblas_gfx950_plan_s* pl, int64_
         int64_t nl = pl->mm_ndense;
         const int32_t* db = pl->mm_dense_blocks;
         int dbg = env_flag("SPBLAS_GFX950_SPMM_DBG") ? std::atoi(std::getenv("SPBLAS_GFX950_SPMM_DBG")) : 0;
-        void* args[] = {&mm, &nn, &rp, &ci, &va, &Bp, &ldb_, &Cp, &ldc_, &al, &be, &db, &wn, &nl, &ch, &dbg};
+        int chd = std::min(ch, MM_DENSE_CH);  // (the probe admitted windows of at most this many rows)
+        void* args[] = {&mm, &nn, &rp, &ci, &va, &Bp, &ldb_, &Cp, &ldc_, &al, &be, &db, &wn, &nl, &chd, &dbg};
         SPB_HIP(hipLaunchKernel(reinterpret_cast<const void*>(spmm_band_mfma_kernel<O>), dim3((unsigned) (8 * cdiv(nl, 8))),
-                                dim3(512), args, ((size_t) ch * MM_NP + (size_t) ((ch + 31) & ~31) * MM_RB) * sizeof(float), s));
+                                dim3(512), args, ((size_t) chd * MM_NP + (size_t) ((chd + 31) & ~31) * MM_RB) * sizeof(float), s));
       }
     } else if (is_panel) {
       const size_t lds = (size_t) (MM_KT * MM_NP + MM_KT * MM_RB + 4 + MM_RB + 4) * sizeof(float);
@@ -1171,6 +1175,7 @@ static int spmm_inspect_typed(spblas_gfx950_handle_t h, spblas_gfx950_plan_s* pl
   int min_per_tile = MM_RB * MM_KT / 12;
   if (const char* e = std::getenv("SPBLAS_GFX950_SPMM_PANEL_MIN"))
     min_per_tile = std::atoi(e) > 0 ? std::atoi(e) : min_per_tile;
+  pl->mm_min_per_tile = min_per_tile;
   // which kernel takes the qualifying blocks: the band kernels (round 6: entry loop over the stored entries, matrix cores for
   // blocks dense in their window) unless SPBLAS_GFX950_SPMM_BAND=0 asks for the tile kernel of rounds 3 - 5.
   // SPBLAS_GFX950_SPMM_BAND_CH: B rows staged per chunk (128 rows: 64 KiB of B + 16 KiB for the dense A tile or the hand-over
@@ -1184,6 +1189,9 @@ static int spmm_inspect_typed(spblas_gfx950_handle_t h, spblas_gfx950_plan_s* pl
     pl->mm_band_ch = ch < 64 ? 64 : (ch > 312 ? 312 : ch);  // (>= one aligned tile of 64 rows: the wide-window path)
     const char* wv = std::getenv("SPBLAS_GFX950_SPMM_BAND_WAVES");
     pl->mm_band_waves = (wv && std::atoi(wv) == 4) ? 4 : (wv && std::atoi(wv) == 16) ? 16 : 8;
+    // the chunk and the waves' hand-over buffers (512 B each) share the 160 KiB of a CU: 312 rows fit beside 8 of them, 304
+    // beside 16 (a launch that asks for more is refused by the runtime)
+    pl->mm_band_ch = std::min(pl->mm_band_ch, MM_LDS_BYTES / 512 - pl->mm_band_waves);
     const char* dn = std::getenv("SPBLAS_GFX950_SPMM_BAND_DENSE");
     // (measured on the banded bench, 2 M rows, 64 entries per row in a window of 128: entry loop 1.41 ms, matrix-core kernel
     // 2.38 ms -- tile build 0.70, contraction 0.59, the rest a skeleton of five barriers and three dependent round trips per
@@ -1213,8 +1221,8 @@ static int spmm_inspect_typed(spblas_gfx950_handle_t h, spblas_gfx950_plan_s* pl
   SPB_HIP(hipMemsetAsync(d_cnt, 0, 16, s));
   hipLaunchKernelGGL((spmm_panel_probe_kernel<O>), dim3((unsigned) pl->mm_nblk), dim3(64), 0, s, pl->m, pl->mm_nblk,
                      static_cast<const O*>(pl->rowptr), pl->colind, pl->n_long > 0 ? pl->win : 0, min_per_tile,
-                     pl->mm_tiles, pl->mm_is_panel, flag32, d_cnt, static_cast<int2*>(pl->mm_win), flag_dense, pl->mm_band_ch,
-                     pl->mm_band_dense_pm);
+                     pl->mm_tiles, pl->mm_is_panel, flag32, d_cnt, static_cast<int2*>(pl->mm_win), flag_dense,
+                     std::min(pl->mm_band_ch, MM_DENSE_CH), pl->mm_band_dense_pm);
   (void) scan_counts_i32(s, pl->mm_nblk, flag32, partials);  // flag32[nblk] = number of qualifying blocks
   hipLaunchKernelGGL(spmm_panel_list_kernel, dim3((unsigned) cdiv(pl->mm_nblk, 256)), dim3(256), 0, s, pl->mm_nblk,
                      pl->mm_is_panel, flag32, pl->mm_panel_blocks);
@@ -1242,12 +1250,15 @@ static int spmm_inspect_typed(spblas_gfx950_handle_t h, spblas_gfx950_plan_s* pl
   pl->mm_panel_nnz = (int64_t) h_cnt[1];
   pl->device_bytes += (size_t) pl->mm_nblk * (1 + 4 * MM_TS + 4 + sizeof(int2) + 8);
   {
-    const int lds = pl->mm_band_ch * MM_NP * (int) sizeof(float) +
-                    std::max(((pl->mm_band_ch + 31) & ~31) * MM_RB * (int) sizeof(float), 16 * 512);
-    SPB_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(spmm_band_kernel<O, 4>), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    SPB_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(spmm_band_kernel<O, 8>), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    SPB_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(spmm_band_kernel<O, 16>), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    SPB_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(spmm_band_mfma_kernel<O>), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+    // each kernel is allowed what it is launched with (a request beyond a workgroup's LDS is refused here, not at the launch)
+    const int chd = std::min(pl->mm_band_ch, MM_DENSE_CH);
+    const int lds_band = pl->mm_band_ch * MM_NP * (int) sizeof(float) + pl->mm_band_waves * 512;
+    const int lds_dense = (chd * MM_NP + ((chd + 31) & ~31) * MM_RB) * (int) sizeof(float);
+    const void* fn = pl->mm_band_waves == 4    ? reinterpret_cast<const void*>(spmm_band_kernel<O, 4>)
+                     : pl->mm_band_waves == 16 ? reinterpret_cast<const void*>(spmm_band_kernel<O, 16>)
+                                               : reinterpret_cast<const void*>(spmm_band_kernel<O, 8>);
+    SPB_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds_band));
+    SPB_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(spmm_band_mfma_kernel<O>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_dense));
   }
   SPB_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(spmm_panel_kernel<O>), hipFuncAttributeMaxDynamicSharedMemorySize,
                               (MM_KT * MM_NP + MM_KT * MM_RB + 4 + MM_RB + 4) * (int) sizeof(float)));
@@ -1378,6 +1389,36 @@ extern "C" int spblas_gfx950_spmm_plan_info(spblas_gfx950_plan_t plan, int64_t i
   info[1] = plan->mm_npanel;      // row blocks (32 rows) multiplied on the matrix cores
   info[2] = plan->mm_panel_nnz;   // entries inside them
   info[3] = plan->mm_ready ? plan->n_long : 0;  // rows cut into parts by the long-row kernel
+  return SPBLAS_GFX950_STATUS_SUCCESS;
+}
+
+// What the inspect decided, block by block (a diagnostic for tests: the counterpart of spblas_gfx950_spmv_t_last).
+extern "C" int spblas_gfx950_spmm_plan_blocks(spblas_gfx950_handle_t handle, spblas_gfx950_plan_t plan, int64_t counts[10],
+                                              unsigned char* kind, int32_t* win, int32_t* tiles) {
+  if (!handle)
+    return SPBLAS_GFX950_STATUS_INVALID_HANDLE;
+  if (!plan || !counts)
+    return SPBLAS_GFX950_STATUS_INVALID_POINTER;
+  if (stream_capturing(handle->stream))
+    return SPBLAS_GFX950_STATUS_NOT_SUPPORTED;
+  for (int i = 0; i < 10; ++i)
+    counts[i] = 0;
+  if (!plan->mm_ready || !plan->mm_is_panel)  // the probe did not run on this plan
+    return SPBLAS_GFX950_STATUS_SUCCESS;
+  const int64_t v[10] = {plan->mm_ready,     plan->mm_nblk,    plan->mm_npanel,     plan->mm_ndense,
+                         plan->mm_panel_nnz, plan->mm_band,    plan->mm_band_ch,    plan->mm_band_waves,
+                         plan->mm_band_dense_pm, plan->mm_min_per_tile};
+  for (int i = 0; i < 10; ++i)
+    counts[i] = v[i];
+  hipStream_t s = handle->stream;
+  const size_t nblk = (size_t) plan->mm_nblk;
+  if (kind)
+    SPB_HIP(hipMemcpyAsync(kind, plan->mm_is_panel, nblk, hipMemcpyDeviceToHost, s));
+  if (win)
+    SPB_HIP(hipMemcpyAsync(win, plan->mm_win, nblk * sizeof(int2), hipMemcpyDeviceToHost, s));
+  if (tiles)
+    SPB_HIP(hipMemcpyAsync(tiles, plan->mm_tiles, nblk * MM_TS * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+  SPB_HIP(hipStreamSynchronize(s));
   return SPBLAS_GFX950_STATUS_SUCCESS;
 }
 
