@@ -215,7 +215,13 @@ int spblas_gfx950_spmv_plan_update_values(spblas_gfx950_handle_t handle, spblas_
  * form holds 1.43 x the matrix instead of 2.43 x. */
 int spblas_gfx950_spmv_plan_detach(spblas_gfx950_handle_t handle, spblas_gfx950_plan_t plan);
 /* A plan carries workspaces (products, partial sums): it must not run on two streams at once.  plan_destroy frees on
- * the handle's current stream, ordered behind the last launch that used the plan on whichever stream that was. */
+ * the handle's current stream, ordered behind the last launch that used the plan on whichever stream that was.  The same
+ * holds for EVERY destroy of this header -- spblas_gfx950_sptrsv_destroy, _ilu0_destroy, _gs_destroy, _multicolor_destroy,
+ * _csr_permute_destroy, _spgemm_destroy -- and for a symbolic pass that replaces the result a SpGEMM state holds: each owner
+ * remembers the stream of its last use, and its arrays are freed (stream-ordered, on the handle's current stream) behind an
+ * event recorded there; the host is not blocked, except that sptrsv_destroy waits for the stream of the last solve before
+ * it releases the plan's pinned status word.  Nothing is inserted while the handle's stream is being captured.  Two USES of
+ * one owner on different streams are not ordered against each other: that stays the caller's business. */
 int spblas_gfx950_plan_destroy(spblas_gfx950_handle_t handle, spblas_gfx950_plan_t plan);
 /* Introspection for tests/bench: info[0]=alg, [1]=window nnz, [2]=#windows,
  * [3]=#long rows, [4]=max row length, [5]=device bytes held, [6]=#column slices,

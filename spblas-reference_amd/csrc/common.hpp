@@ -139,6 +139,45 @@ inline void dev_free(void* p, hipStream_t s) {
   }
 }
 
+// Where an owner of device arrays (a plan, a solver's info, a SpGEMM state) was last used.  Every entry point that launches
+// work reading or writing the owner's arrays notes its stream; what frees or rewrites those arrays later, on whatever
+// stream the handle then sits, puts itself behind that last use first.  Two uses are never ordered against each other:
+// one owner on two streams at once stays the caller's error.
+struct use_record {
+  hipStream_t last = nullptr;
+  bool used = false;
+};
+
+inline void note_use(use_record& rec, hipStream_t s) {
+  rec.last = s;
+  rec.used = true;
+}
+
+// Work submitted to `s` from here on runs after the last noted use: an event recorded on that stream, waited for on `s`
+// (device side; the host does not block), a host-side drain of the last stream where the event cannot be had.  Nothing is
+// inserted while `s` is being captured: an eager earlier use cannot be joined to a capture.
+inline void order_behind_last_use(const use_record& rec, hipStream_t s) {
+  if (!rec.used || rec.last == s || stream_capturing(s))
+    return;
+  hipEvent_t ev = nullptr;
+  if (hipEventCreateWithFlags(&ev, hipEventDisableTiming) == hipSuccess) {
+    if (hipEventRecord(ev, rec.last) != hipSuccess || hipStreamWaitEvent(s, ev, 0) != hipSuccess)
+      (void) hipStreamSynchronize(rec.last);
+    (void) hipEventDestroy(ev);
+  } else {
+    (void) hipStreamSynchronize(rec.last);
+  }
+  (void) hipGetLastError();
+}
+
+// The host-side form, for what the host itself is about to touch (pinned words, host-written plan arrays): returns once
+// the last use has finished.  `s` = the stream the caller goes on with; nullptr drains the last stream whichever it is.
+inline hipError_t drain_last_use(const use_record& rec, hipStream_t s) {
+  if (!rec.used || (s && rec.last == s))
+    return hipSuccess;
+  return hipStreamSynchronize(rec.last);
+}
+
 // `bytes` of handle-owned scratch, valid until the next handle_scratch call on this handle.  Work that
 // used the previous contents is ordered before the new user by the stream; when the stream changed or
 // the buffer has to grow, the old stream is drained first.

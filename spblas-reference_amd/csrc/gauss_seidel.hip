@@ -44,6 +44,7 @@ struct spblas_gfx950_gs_s {
   std::vector<int32_t> h_color_ptr;  // [colours + 1]
   int32_t* diag = nullptr;           // [m] position of row r's diagonal entry in colind / values
   int32_t* perm = nullptr;           // [m] the plan's own copy of the row order; nullptr: the rows themselves
+  spb::use_record use;               // the stream of the last sweep: destroy frees behind it
 };
 
 namespace spb {
@@ -227,6 +228,7 @@ int spblas_gfx950_gs_destroy(spblas_gfx950_handle_t handle, spblas_gfx950_gs_t p
     return SPBLAS_GFX950_STATUS_INVALID_HANDLE;
   if (!plan)
     return SPBLAS_GFX950_STATUS_SUCCESS;
+  order_behind_last_use(plan->use, handle->stream);  // the last sweep may have run elsewhere and still read these
   dev_free(plan->diag, handle->stream);
   dev_free(plan->perm, handle->stream);
   delete plan;
@@ -336,6 +338,7 @@ int spblas_gfx950_gs_sweep(spblas_gfx950_handle_t handle, spblas_gfx950_gs_t pla
     return SPBLAS_GFX950_STATUS_PLAN_MISMATCH;
   if (m == 0 || sweeps == 0)
     return SPBLAS_GFX950_STATUS_SUCCESS;
+  note_use(plan->use, handle->stream);
   if (value_type == SPBLAS_GFX950_F32)
     return gs_sweep_lanes<float>(handle, plan, sweeps, direction, rowptr, colind, values, omega, b, x);
   return gs_sweep_lanes<double>(handle, plan, sweeps, direction, rowptr, colind, values, omega, b, x);

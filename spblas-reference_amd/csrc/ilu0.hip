@@ -53,6 +53,13 @@ struct spblas_gfx950_ilu0_s {
   spblas_gfx950_trsv_t levels = nullptr;  // the LOWER level plan (spblas_gfx950_sptrsv_create), read only
   int32_t* diag = nullptr;                // [m] position of each row's diagonal entry in colind / values
   unsigned* status = nullptr;             // [4] word 0: 0 = every pivot fine, else 0xFFFFFFFF - the smallest row whose pivot is not
+  spb::use_record use;                    // the stream of the last factor / sweeps / status call: destroy frees behind it
+
+  void note(hipStream_t s) {  // ... which also read the level plan this one owns
+    spb::note_use(use, s);
+    if (levels)
+      spb::note_use(levels->use, s);
+  }
 };
 
 namespace spb {
@@ -350,6 +357,7 @@ template <typename T>
 static int ilu0_factor_typed(spblas_gfx950_handle_t h, spblas_gfx950_ilu0_s* pl, const int32_t* rowptr, const int32_t* colind,
                              const T* a_values, T* lu_values) {
   hipStream_t s = h->stream;
+  pl->note(s);
   const spblas_gfx950_trsv_s* lv = pl->levels;
   if (a_values != lu_values && pl->nnz > 0)
     SPB_HIP(hipMemcpyAsync(lu_values, a_values, (size_t) pl->nnz * sizeof(T), hipMemcpyDeviceToDevice, s));
@@ -379,6 +387,7 @@ template <typename T>
 static int ilu0_sweeps_typed(spblas_gfx950_handle_t h, spblas_gfx950_ilu0_s* pl, int sweeps, const int32_t* rowptr,
                              const int32_t* colind, const T* a_values, T* lu_values, T* work) {
   hipStream_t s = h->stream;
+  pl->note(s);
   const spblas_gfx950_trsv_s* lv = pl->levels;
   // a row of level l is final from sweep l on: more than levels - 1 sweeps change nothing
   const int levels = lv->h_level_ptr.empty() ? 0 : (int) lv->h_level_ptr.size() - 1;
@@ -415,6 +424,7 @@ int spblas_gfx950_ilu0_destroy(spblas_gfx950_handle_t handle, spblas_gfx950_ilu0
     return SPBLAS_GFX950_STATUS_INVALID_HANDLE;
   if (!plan)
     return SPBLAS_GFX950_STATUS_SUCCESS;
+  order_behind_last_use(plan->use, handle->stream);  // (the level plan's destroy does the same for itself)
   (void) spblas_gfx950_sptrsv_destroy(handle, plan->levels);
   dev_free(plan->diag, handle->stream);
   dev_free(plan->status, handle->stream);
@@ -486,6 +496,7 @@ int spblas_gfx950_ilu0_status(spblas_gfx950_handle_t handle, spblas_gfx950_ilu0_
     return SPBLAS_GFX950_STATUS_INVALID_POINTER;
   if (stream_capturing(handle->stream))
     return SPBLAS_GFX950_STATUS_NOT_SUPPORTED;
+  plan->note(handle->stream);
   unsigned st = 0;
   SPB_HIP(hipMemcpyAsync(&st, plan->status, sizeof(unsigned), hipMemcpyDeviceToHost, handle->stream));
   SPB_HIP(hipStreamSynchronize(handle->stream));

@@ -52,11 +52,13 @@ struct spblas_gfx950_multicolor_s {
   int32_t* perm = nullptr;       // [m] new -> old, sorted by (colour, old index)
   int32_t* inv_perm = nullptr;   // [m] old -> new
   int32_t* color_ptr = nullptr;  // [colours + 1] first new index of every colour
+  spb::use_record use;           // the stream of the last copy out of the plan: destroy frees behind it
 };
 
 struct spblas_gfx950_permute_s {
   int64_t m = 0, nnz = 0;
   int32_t* map = nullptr;  // [nnz] position in A's arrays of B's entry p
+  spb::use_record use;     // the stream of the last gather through the map: destroy frees behind it
 };
 
 namespace spb {
@@ -213,6 +215,7 @@ int spblas_gfx950_multicolor_destroy(spblas_gfx950_handle_t handle, spblas_gfx95
     return SPBLAS_GFX950_STATUS_INVALID_HANDLE;
   if (!plan)
     return SPBLAS_GFX950_STATUS_SUCCESS;
+  order_behind_last_use(plan->use, handle->stream);
   dev_free(plan->color, handle->stream);
   dev_free(plan->perm, handle->stream);
   dev_free(plan->inv_perm, handle->stream);
@@ -335,6 +338,7 @@ int spblas_gfx950_multicolor_copy(spblas_gfx950_handle_t handle, spblas_gfx950_m
   if (!plan)
     return SPBLAS_GFX950_STATUS_INVALID_POINTER;
   hipStream_t s = handle->stream;
+  note_use(plan->use, s);
   const size_t mb = (size_t) plan->m * 4;
   if (perm && mb)
     SPB_HIP(hipMemcpyAsync(perm, plan->perm, mb, hipMemcpyDeviceToDevice, s));
@@ -352,6 +356,7 @@ int spblas_gfx950_csr_permute_destroy(spblas_gfx950_handle_t handle, spblas_gfx9
     return SPBLAS_GFX950_STATUS_INVALID_HANDLE;
   if (!plan)
     return SPBLAS_GFX950_STATUS_SUCCESS;
+  order_behind_last_use(plan->use, handle->stream);
   dev_free(plan->map, handle->stream);
   delete plan;
   return SPBLAS_GFX950_STATUS_SUCCESS;
@@ -443,6 +448,7 @@ int spblas_gfx950_csr_permute_values(spblas_gfx950_handle_t handle, spblas_gfx95
     return SPBLAS_GFX950_STATUS_INVALID_VALUE;
   if (nnz == 0)
     return SPBLAS_GFX950_STATUS_SUCCESS;
+  note_use(plan->use, handle->stream);
   const dim3 grid(stride_grid(handle, nnz)), block(256);
   if (value_type == SPBLAS_GFX950_F32)
     hipLaunchKernelGGL(pm_gather_kernel<uint32_t>, grid, block, 0, handle->stream, nnz, plan->map,

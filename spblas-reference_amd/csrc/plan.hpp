@@ -113,8 +113,7 @@ struct spblas_gfx950_plan_s {
   bool hub_rows_owned = false;
   // the stream of the last launch that used the plan's workspaces: plan_destroy orders its frees behind it.  (A plan
   // carries mutable workspaces -- products, partial sums, long-row partials -- and must not run on two streams at once.)
-  hipStream_t last_stream = nullptr;
-  bool used = false;
+  spb::use_record use;
   // spblas_gfx950_spmv_plan_detach: the plan is self-contained (SLICED snapshot, no hub rows, no hot split) and its owner has
   // released the structure / value arrays it was built from -- multiplies take no array arguments, the values cannot be refreshed
   int detached = 0;

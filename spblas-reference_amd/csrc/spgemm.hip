@@ -99,6 +99,7 @@ struct spblas_gfx950_spgemm_s {
   int32_t* sym_flag = nullptr;  // symbolic pass only: [n_sortable] 1 = no two products of the row share a column
   bool r_ready = false;
   int numeric_calls = 0;        // numeric passes since the symbolic one (the SECOND records: a one-shot fill pays nothing)
+  spb::use_record use;          // the stream of the last symbolic / numeric pass: release and destroy free behind it
 };
 
 namespace spb {
@@ -1831,6 +1832,7 @@ static int spgemm_numeric_typed(spblas_gfx950_handle_t h, spblas_gfx950_spgemm_s
 }
 
 static void spgemm_release(spblas_gfx950_spgemm_s* st, hipStream_t s) {
+  order_behind_last_use(st->use, s);  // a fill may still be reading these on the stream it was issued on
   dev_free(st->rowptr, s);
   dev_free(st->perm, s);
   dev_free(st->dense_bits, s);
@@ -1941,6 +1943,7 @@ static int spgemm_symbolic_impl(spblas_gfx950_handle_t handle, spblas_gfx950_spg
     return SPBLAS_GFX950_STATUS_INVALID_SIZE;
   hipStream_t s = handle->stream;
   spgemm_release(st, s);
+  note_use(st->use, s);
   st->has_addend = st->d_rowptr != nullptr;
   st->identity_b = identity_b;
   st->m = m; st->k = k; st->n = n; st->a_nnz = a_nnz; st->b_nnz = b_nnz;
@@ -2118,6 +2121,7 @@ static int spgemm_numeric_impl(spblas_gfx950_handle_t handle, spblas_gfx950_spge
                         (!st->identity_b && st->b_nnz > 0 && (!b_values || !b_colind))))
     return SPBLAS_GFX950_STATUS_INVALID_POINTER;
   hipStream_t s = handle->stream;
+  note_use(st->use, s);
   // pointers may be rebound between calls as long as the pattern is unchanged
   // (multiply_spgemm.hpp:195-208 rebinds them with rocsparse_csr_set_pointers)
   st->a_rowptr = a_rowptr; st->a_colind = a_colind; st->b_rowptr = b_rowptr; st->b_colind = b_colind;

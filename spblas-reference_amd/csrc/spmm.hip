@@ -1311,8 +1311,7 @@ extern "C" int spblas_gfx950_spmm(spblas_gfx950_handle_t handle, spblas_gfx950_p
   if (plan && !plan_matches(*plan, m, k, nnz, rowptr, colind, offset_type, value_type))
     return SPBLAS_GFX950_STATUS_PLAN_MISMATCH;
   if (plan) {  // the long-row partials are the plan's
-    plan->last_stream = handle->stream;
-    plan->used = true;
+    note_use(plan->use, handle->stream);
   }
   if (value_type == SPBLAS_GFX950_F32) {
     return offset_type == SPBLAS_GFX950_I32

@@ -891,8 +891,7 @@ static int spmv_typed(spblas_gfx950_handle_t h, spblas_gfx950_plan_s* pl, int op
     return spmv_sliced_exec(h, pl, alpha_p, x_p, beta_p, y_p);
 
   if (pl && pl->alg == SPBLAS_GFX950_SPMV_ROWBLOCK) {
-    pl->last_stream = s;  // part_head / part_tail are the plan's
-    pl->used = true;
+    note_use(pl->use, s);  // part_head / part_tail are the plan's
     if (pl->n_long > 0) {
       launch_rowblock<T, O, true>(s, pl, rowptr, colind, values, x, y, alpha, beta);
       hipLaunchKernelGGL((spmv_long_fixup_kernel<T, O>), dim3((unsigned) pl->n_long), dim3(64), 0, s,
@@ -1616,19 +1615,8 @@ int spblas_gfx950_plan_destroy(spblas_gfx950_handle_t handle, spblas_gfx950_plan
     return SPBLAS_GFX950_STATUS_INVALID_HANDLE;
   if (!plan)
     return SPBLAS_GFX950_STATUS_SUCCESS;
-  hipStream_t s = handle->stream;
-  if (plan->used && plan->last_stream != s) {
-    // the frees below are ordered on the handle's stream: put them behind the last launch that used the plan
-    hipEvent_t ev = nullptr;
-    if (hipEventCreateWithFlags(&ev, hipEventDisableTiming) == hipSuccess) {
-      if (hipEventRecord(ev, plan->last_stream) != hipSuccess || hipStreamWaitEvent(s, ev, 0) != hipSuccess)
-        (void) hipStreamSynchronize(plan->last_stream);
-      (void) hipEventDestroy(ev);
-    } else {
-      (void) hipStreamSynchronize(plan->last_stream);
-    }
-    (void) hipGetLastError();
-  }
+  // the frees below are ordered on the handle's stream: put them behind the last launch that used the plan
+  order_behind_last_use(plan->use, handle->stream);
   spmv_plan_release(handle, plan);
   return SPBLAS_GFX950_STATUS_SUCCESS;
 }

@@ -538,8 +538,7 @@ static int hot_launch(spblas_gfx950_handle_t h, spblas_gfx950_plan_s* pl, const 
   const O* rowptr = static_cast<const O*>(hp->rowptr);
   T* head = static_cast<T*>(pl->hot_part);
   T* tail = head + hp->nwin;
-  hp->last_stream = s;
-  hp->used = true;
+  note_use(hp->use, s);
   hipLaunchKernelGGL((pb_hot_rows_kernel<T, O>), dim3((unsigned) grid), dim3(HOT_THREADS), HOT_LDS, s, hp->nnz, hp->nwin, rowptr,
                      pl->hot_col, static_cast<const T*>(pl->hot_val), pl->hot_cols, pl->hot_k, static_cast<const T*>(x),
                      static_cast<T*>(y), alpha, pl->hot_rows, (int) pl->hot_m, hp->win_row, head, tail);
@@ -564,8 +563,7 @@ int spmv_sliced_reduce_rows(spblas_gfx950_handle_t h, spblas_gfx950_plan_s* pl, 
 
 int spmv_hot_exec(spblas_gfx950_handle_t h, spblas_gfx950_plan_s* pl, const void* alpha, const void* x, const void* beta,
                   void* y) {
-  pl->last_stream = h->stream;
-  pl->used = true;
+  note_use(pl->use, h->stream);
   pl->rest_plan->nt_products = pl->nt_products;
   const int rc = spmv_sliced_exec(h, pl->rest_plan, alpha, x, beta, y);
   if (rc)

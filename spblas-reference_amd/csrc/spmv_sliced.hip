@@ -3332,8 +3332,7 @@ int spmv_sliced_update(spblas_gfx950_handle_t h, spblas_gfx950_plan_s* pl, const
   if (!have_src && !pl->is_child) {
     if (stream_capturing(h->stream))
       return SPBLAS_GFX950_STATUS_NOT_SUPPORTED;
-    if (pl->used && pl->last_stream != h->stream)
-      SPB_HIP(hipStreamSynchronize(pl->last_stream));
+    SPB_HIP(drain_last_use(pl->use, h->stream));
     const int nt = pl->nt_products, refresh = pl->refresh_each_call;
     spmv_sliced_free(h, pl);
     pl->device_bytes = pl->base_device_bytes;
@@ -3386,8 +3385,7 @@ static int pick_ksplit(int64_t waves, int64_t steps_per_bin) {
 template <typename T>
 static int sliced_expand_typed(spblas_gfx950_handle_t h, spblas_gfx950_plan_s* pl, const void* x) {
   pl->last_x = x;  // the hub rows are computed in the reduce stage and gather x themselves
-  pl->last_stream = h->stream;
-  pl->used = true;
+  note_use(pl->use, h->stream);
   // one wave of workgroups (2 per CU with 80 KiB slices, 1 with 160 KiB), but never shares so small that
   // re-loading the x slice dominates
   const int4* items = static_cast<const int4*>(pl->s_xitems);
@@ -3506,8 +3504,7 @@ static int sliced_reduce_typed(spblas_gfx950_handle_t h, spblas_gfx950_plan_s* p
   hipStream_t s = h->stream;
   if (wb_end <= wb_begin)
     return SPBLAS_GFX950_STATUS_SUCCESS;
-  pl->last_stream = s;
-  pl->used = true;
+  note_use(pl->use, s);
   if (peers_p && pl->hub_len > 0 && pl->n_hub > 0)
     return SPBLAS_GFX950_STATUS_NOT_SUPPORTED;  // the fused all-gather epilogue does not cover hub rows
   const T alpha = *static_cast<const T*>(alpha_p), beta = *static_cast<const T*>(beta_p);

@@ -628,6 +628,7 @@ int trsv_begin_solve(spblas_gfx950_handle_t h, spblas_gfx950_trsv_s* pl, bool* c
   *bar_off_out = bar_off;
   if (capturing && !pl->tickets)
     return SPBLAS_GFX950_STATUS_NOT_SUPPORTED;
+  note_use(pl->use, s);  // (vector and block solve alike: both start here)
   if (!pl->tickets) {
     int rc = dev_alloc((void**) &pl->tickets, ctl_ints * 4, s);
     if (rc)
@@ -911,12 +912,16 @@ int spblas_gfx950_sptrsv_destroy(spblas_gfx950_handle_t handle, spblas_gfx950_tr
     return SPBLAS_GFX950_STATUS_INVALID_HANDLE;
   if (!plan)
     return SPBLAS_GFX950_STATUS_SUCCESS;
+  // the frees are ordered on the handle's stream: put them behind the last solve, wherever it ran
+  order_behind_last_use(plan->use, handle->stream);
   dev_free(plan->order, handle->stream);
   dev_free(plan->level_ptr, handle->stream);
   dev_free(plan->tickets, handle->stream);
   if (plan->sticky) {
-    // (the kernel of the last solve may still be running: the word must outlive it)
-    (void) hipStreamSynchronize(handle->stream);
+    // (the kernel of the last solve may still be running and writes this HOST word: it must have finished, on the stream
+    // it ran on, not merely be ordered in front of something)
+    (void) drain_last_use(plan->use, nullptr);
+    (void) hipGetLastError();
     (void) hipHostFree(plan->sticky);
   }
   delete plan;

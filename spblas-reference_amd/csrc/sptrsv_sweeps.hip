@@ -205,6 +205,8 @@ int spblas_gfx950_sptrsv_sweeps(spblas_gfx950_handle_t handle, spblas_gfx950_trs
     return SPBLAS_GFX950_STATUS_INVALID_VALUE;
   if (m == 0)
     return SPBLAS_GFX950_STATUS_SUCCESS;
+  if (plan)
+    note_use(plan->use, handle->stream);  // (the sweeps walk the plan's row order)
   const int lanes = lanes_per_row(m, nnz);  // sptrsv_create's call: with and without a plan the same lanes, hence the same bits
   const int upper = uplo == SPBLAS_GFX950_UPPER, unit = diag == SPBLAS_GFX950_DIAG_UNIT;
   if (value_type == SPBLAS_GFX950_F32)

@@ -24,6 +24,7 @@ struct spblas_gfx950_trsv_s {
   // pinned, device-visible host word: a solve whose grid barrier ran into its poll bound sets it (system-scope store, only
   // on that path), the NEXT solve on this plan -- and spblas_gfx950_sptrsv_status -- reads it without touching the stream
   int* sticky = nullptr;
+  spb::use_record use;  // the stream of the last solve / sweep / factorisation that read the plan: destroy frees behind it
 };
 
 namespace spb {

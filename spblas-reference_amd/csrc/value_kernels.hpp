@@ -446,8 +446,7 @@ static int vk_spmv(spblas_gfx950_handle_t h, spblas_gfx950_plan_s* pl, int64_t m
     return SPBLAS_GFX950_STATUS_SUCCESS;
   }
   if (pl && pl->alg == SPBLAS_GFX950_SPMV_ROWBLOCK && pl->win == VT::window) {
-    pl->last_stream = s;  // part_head / part_tail are the plan's
-    pl->used = true;
+    note_use(pl->use, s);  // part_head / part_tail are the plan's
     acc_t* ph = static_cast<acc_t*>(pl->part_head);
     acc_t* pt = static_cast<acc_t*>(pl->part_tail);
     if (pl->n_long > 0) {
@@ -517,8 +516,7 @@ static int vk_spmm(spblas_gfx950_handle_t h, spblas_gfx950_plan_s* pl, int64_t m
       pl->mm_long_cap = need;
       pl->mm_long_parts = (int) parts;
     }
-    pl->last_stream = s;
-    pl->used = true;
+    note_use(pl->use, s);
   }
   if (ccs == 1 && bcs == 1) {
     // layout_right: 16-byte gathers (VT::wide elements) when B and C allow them
