@@ -565,6 +565,21 @@ int spblas_gfx950_sptrsm_solve(spblas_gfx950_handle_t handle, spblas_gfx950_trsv
                                int64_t n, const void* alpha, const int32_t* rowptr, const int32_t* colind,
                                const void* values, const void* B, int64_t b_row_stride, int64_t b_col_stride,
                                void* X, int64_t x_row_stride, int64_t x_col_stride, int value_type);
+/* What the last sptrsm_solve on this handle decided (a diagnostic for tests, like spmv_t_last; host integers only: no kernel
+ * runs, nothing is synchronised).  Writes min(n_out, 8) entries: out[0] = path (SPTRSM_NONE before the first such call,
+ * SPTRSM_FORWARDED: n == 1 with two contiguous vectors, the call went to sptrsv_solve and [1] .. [7] are 0, SPTRSM_ELEMENTS:
+ * every element of X through its strides, SPTRSM_PIECES: whole units of X as 16-byte pieces); [1] = elements of X's base past
+ * a 16-byte boundary (0 on the element path); [2] = units of 16 bytes a row of X is cut into, the partial ones in front and
+ * behind included; [3] = log2 of the unit lanes C of a team; [4] = its entry lanes E = min(lanes per row of the plan, 64 / C);
+ * [5] = 1 if whole units of B are read as 16-byte pieces too; [6] = bytes the buffer descriptor of X spans (0 on the element
+ * path); [7] = passes of a team over the units of a row, ceil(units / C).  A call refused before it launched (a status other
+ * than success from the argument checks or the plan's entry protocol) leaves the previous report.  Changes nothing about
+ * the solve. */
+#define SPBLAS_GFX950_SPTRSM_NONE 0
+#define SPBLAS_GFX950_SPTRSM_FORWARDED 1
+#define SPBLAS_GFX950_SPTRSM_ELEMENTS 2
+#define SPBLAS_GFX950_SPTRSM_PIECES 3
+int spblas_gfx950_sptrsm_last(spblas_gfx950_handle_t handle, int64_t* out, int n_out);
 /* An APPROXIMATE solve by Jacobi sweeps on the triangular system (the iterative sparse triangular solve of Anzt, Chow and
  * Dongarra; no reference counterpart): what a preconditioner apply needs, at the price of `sweeps + 1` SpMV-shaped launches
  * instead of one hand-off per level.  The triangle read is the one sptrsv_solve reads (strict part named by uplo, the LAST

@@ -34,6 +34,7 @@ GS_FORWARD, GS_BACKWARD, GS_SYMMETRIC = 0, 1, 2
 SPMV_AUTO, SPMV_VECTOR, SPMV_ROWBLOCK, SPMV_SLICED = 0, 1, 2, 3
 SPMV_T_NONE, SPMV_T_SCATTER, SPMV_T_TWO_PASS = 0, 1, 2                                       # spmv_t_last: out[0]
 SPMV_T_NOT_WANTED, SPMV_T_DOES_NOT_FIT, SPMV_T_CAPTURING, SPMV_T_NO_SCRATCH = 1, 2, 3, 4    # ... and out[1]
+SPTRSM_NONE, SPTRSM_FORWARDED, SPTRSM_ELEMENTS, SPTRSM_PIECES = 0, 1, 2, 3                    # sptrsm_last: out[0]
 OPT_BIN_ROW_ALIGN = 1
 OPT_MAX_KSPLIT = 2
 OPT_VALUE_SNAPSHOT = 3
@@ -124,6 +125,7 @@ PROTOTYPES = [
     ("spblas_gfx950_sptrsm_solve", c_int,
      [c_void_p, c_void_p, c_i64, c_i64, c_i64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_i64, c_void_p,
       c_i64, c_i64, c_int]),
+    ("spblas_gfx950_sptrsm_last", c_int, [c_void_p, ctypes.POINTER(c_i64), c_int]),
     ("spblas_gfx950_sptrsv_sweeps", c_int,
      [c_void_p, c_void_p, c_i64, c_i64, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
       c_void_p, c_int]),

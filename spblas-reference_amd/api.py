@@ -277,6 +277,15 @@ class _Handle:
             out["n_items"] = arr[7]
         return out
 
+    def sptrsm_last(self):
+        """What the last triangular solve with a block of right-hand sides on this handle decided (spblas_gfx950_sptrsm_last;
+        a diagnostic, host integers only): path 0 none yet, 1 forwarded to the vector solve, 2 element kernels, 3 16-byte
+        pieces; X's misalignment in elements, the units per row, log2 of the unit lanes C and the entry lanes E of a team,
+        whether B is read in pieces, the bytes X's buffer descriptor spans and the passes ceil(units / C) of the unit loop."""
+        arr = (ctypes.c_int64 * 8)()
+        check(_capi.lib().spblas_gfx950_sptrsm_last(self.h, arr, 8), "spblas_gfx950_sptrsm_last")
+        return dict(zip(("path", "mis", "units", "logC", "E", "b_piece", "x_bytes", "passes"), list(arr)))
+
     @classmethod
     def current(cls, device):
         if device.type != "cuda":

@@ -66,6 +66,13 @@ struct spblas_gfx950_handle_s {
     uint64_t epoch = 0;
     hipStream_t stream = nullptr;
   } spmv_t_last;
+  // what the last block triangular solve on this handle decided (spblas_gfx950_sptrsm_last: a diagnostic for tests).  Host
+  // integers written by trsm_solve_typed next to its decision (path 1: the call was forwarded to the vector solve).
+  struct sptrsm_last_t {
+    int path = 0;  // SPBLAS_GFX950_SPTRSM_* of spblas_gfx950.h
+    int mis = 0, units = 0, logC = 0, E = 0, b_piece = 0;
+    int64_t x_bytes = 0, passes = 0;
+  } sptrsm_last;
   // pinned, device-visible host buffer for small read-backs (spb::readback_*), and the copies staged in it
   void* pinned = nullptr;
   size_t pinned_bytes = 0, pinned_used = 0;

@@ -254,6 +254,15 @@ static int trsm_solve_typed(spblas_gfx950_handle_t h, spblas_gfx950_trsv_s* pl, 
     ++logC;
   a.logC = logC;
   a.E = pl->lanes < (SPB_WAVE >> logC) ? pl->lanes : (SPB_WAVE >> logC);
+  auto& last = h->sptrsm_last;  // the decision, for spblas_gfx950_sptrsm_last
+  last.path = vec ? SPBLAS_GFX950_SPTRSM_PIECES : SPBLAS_GFX950_SPTRSM_ELEMENTS;
+  last.mis = a.mis;
+  last.units = a.units;
+  last.logC = a.logC;
+  last.E = a.E;
+  last.b_piece = a.b_piece;
+  last.x_bytes = a.x_bytes;
+  last.passes = cdiv(a.units, (int64_t) 1 << logC);
   return vec ? trsm_launch<T, true>(h, pl, a) : trsm_launch<T, false>(h, pl, a);
 }
 
@@ -284,8 +293,14 @@ extern "C" int spblas_gfx950_sptrsm_solve(spblas_gfx950_handle_t handle, spblas_
     return SPBLAS_GFX950_STATUS_INVALID_SIZE;
   if (m == 0 || n == 0)
     return SPBLAS_GFX950_STATUS_SUCCESS;
-  if (n == 1 && (m == 1 || (brs == 1 && xrs == 1)))  // two contiguous vectors: the vector solve itself, bit for bit
-    return spblas_gfx950_sptrsv_solve(handle, plan, m, nnz, alpha, rowptr, colind, values, B, X, value_type);
+  if (n == 1 && (m == 1 || (brs == 1 && xrs == 1))) {  // two contiguous vectors: the vector solve itself, bit for bit
+    const int rc = spblas_gfx950_sptrsv_solve(handle, plan, m, nnz, alpha, rowptr, colind, values, B, X, value_type);
+    if (rc == SPBLAS_GFX950_STATUS_SUCCESS) {
+      handle->sptrsm_last = {};
+      handle->sptrsm_last.path = SPBLAS_GFX950_SPTRSM_FORWARDED;
+    }
+    return rc;
+  }
   if (value_type == SPBLAS_GFX950_F32)
     return trsm_solve_typed<float>(handle, plan, n, rowptr, colind, static_cast<const float*>(values),
                                    *static_cast<const float*>(alpha), static_cast<const float*>(B), brs, bcs,
@@ -293,6 +308,21 @@ extern "C" int spblas_gfx950_sptrsm_solve(spblas_gfx950_handle_t handle, spblas_
   return trsm_solve_typed<double>(handle, plan, n, rowptr, colind, static_cast<const double*>(values),
                                   *static_cast<const double*>(alpha), static_cast<const double*>(B), brs, bcs,
                                   static_cast<double*>(X), xrs, xcs);
+}
+
+// What the last block solve on this handle decided (a diagnostic for tests: the counterpart of spblas_gfx950_spmv_t_last).
+extern "C" int spblas_gfx950_sptrsm_last(spblas_gfx950_handle_t handle, int64_t* out, int n_out) {
+  if (!handle)
+    return SPBLAS_GFX950_STATUS_INVALID_HANDLE;
+  if (!out)
+    return SPBLAS_GFX950_STATUS_INVALID_POINTER;
+  if (n_out < 1)
+    return SPBLAS_GFX950_STATUS_INVALID_SIZE;
+  const auto& last = handle->sptrsm_last;
+  const int64_t v[8] = {last.path, last.mis, last.units, last.logC, last.E, last.b_piece, last.x_bytes, last.passes};
+  for (int i = 0; i < n_out && i < 8; ++i)
+    out[i] = v[i];
+  return SPBLAS_GFX950_STATUS_SUCCESS;
 }
 
 // Loads this file's code object at handle creation (handle.hip), as the other files do.
