@@ -246,6 +246,18 @@ int spblas_gfx950_plan_info_sliced(spblas_gfx950_plan_t plan, int64_t info[12]);
  * left to the tiles, [5] device bytes of the tiled part, [6] windows of 256 entries the hot part is cut into, [7] = 0.
  * All 0 for a plan without the split. */
 int spblas_gfx950_plan_info_hot(spblas_gfx950_plan_t plan, int64_t info[8]);
+/* What the inspect laid out for the hot part of such a plan (a diagnostic for tests, like spmm_plan_blocks; no kernel
+ * runs).  counts: [0] sampled references from which a column was taken, [1] hot columns K, [2] entries of A_hot, [3] rows
+ * that have such entries, [4] windows of 256 entries, [5] rows that lie in more than one window, [6] workgroups the
+ * multiply will launch (SPBLAS_GFX950_PB_HOT_GRID at inspect sets it: a test hook), [7] splits below this plan (2: the
+ * remainder was split again, SPBLAS_GFX950_PB_HOT_DEPTH).  hot_cols ([1] ascending column numbers), hot_rows ([3] rows of
+ * y), hot_rowptr ([3] + 1 offsets into A_hot, always 64 bits), win_row ([4] + 1: first row of A_hot that starts at or
+ * behind each window's first entry) and cross_rows ([5] rows of A_hot, in no particular order) are HOST arrays, each may
+ * be NULL; they are copied on the handle's stream, which is synchronised once.  A plan without the split reports eight
+ * zeros and copies nothing.  NOT_SUPPORTED while the stream is capturing. */
+int spblas_gfx950_plan_hot_layout(spblas_gfx950_handle_t handle, spblas_gfx950_plan_t plan, int64_t counts[8],
+                                  int32_t* hot_cols, int32_t* hot_rows, int64_t* hot_rowptr, int32_t* win_row,
+                                  int32_t* cross_rows);
 
 /* Two-stage execution of a SLICED plan (other plans: STATUS_NOT_SUPPORTED), used to overlap the
  * multi-GPU all-gather of finished y rows with the rest of the SpMV:

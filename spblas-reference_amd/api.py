@@ -435,6 +435,28 @@ class _Plan:
         out.update(kind=kind, win=win, tiles=tiles)
         return out
 
+    def hot_layout(self):
+        """What the inspect laid out for the hot-column part of a split SLICED plan (spblas_gfx950_plan_hot_layout; a
+        diagnostic, like spmm_blocks): the counts, and as numpy arrays the hot columns (ascending), the rows of y that have
+        hot entries, their offsets into A_hot (int64), the first row of every window and the rows that lie in more than one
+        window (sorted here: the device lists them in the order of an atomic).  SYNCHRONISES the calling thread's stream.
+        All counts zero and empty arrays for a plan without the split."""
+        names = ("thr", "k", "n_hot", "m_hot", "nwin", "n_cross", "grid", "depth")
+        fn, h = _capi.lib().spblas_gfx950_plan_hot_layout, self._calling_handle().h
+        arr = (ctypes.c_int64 * 8)()
+        check(fn(h, self.plan, arr, None, None, None, None, None), "spblas_gfx950_plan_hot_layout")
+        out = dict(zip(names, list(arr)))
+        split = out["k"] > 0
+        cols, rows = np.zeros(out["k"], np.int32), np.zeros(out["m_hot"], np.int32)
+        rowptr = np.zeros(out["m_hot"] + 1 if split else 0, np.int64)
+        win_row = np.zeros(out["nwin"] + 1 if split else 0, np.int32)
+        cross = np.zeros(out["n_cross"], np.int32)
+        if split:
+            check(fn(h, self.plan, arr, cols.ctypes.data, rows.ctypes.data, rowptr.ctypes.data, win_row.ctypes.data,
+                     cross.ctypes.data), "spblas_gfx950_plan_hot_layout")
+        out.update(hot_cols=cols, hot_rows=rows, hot_rowptr=rowptr, win_row=win_row, cross_rows=np.sort(cross))
+        return out
+
     def update_values(self, values):
         """Refresh the plan after A's values changed in place (only the SLICED re-tiling keeps
         a copy of them; the other algorithms read the caller's array on every call)."""

@@ -161,6 +161,8 @@ struct spblas_gfx950_plan_s {
   void* hot_part = nullptr;      // T[2 * nwin]: per window of A_hot the piece of the row that runs in / the row that runs on
   int32_t* hot_cross = nullptr;  // [hot_ncross] rows of A_hot that lie in more than one window
   int64_t hot_ncross = 0;
+  int hot_thr = 0;               // sampled references from which a column was taken (spblas_gfx950_plan_hot_layout)
+  int hot_grid = 0;              // > 0: workgroups of the multiply (SPBLAS_GFX950_PB_HOT_GRID at inspect: a test hook)
   void* rest_rowptr = nullptr;   // O[m + 1]
   int32_t* rest_col = nullptr;   // [nnz - hot_nnz]
   void* rest_val = nullptr;      // T[nnz - hot_nnz]

@@ -9,7 +9,7 @@
 // time, so the entries that reference them are multiplied in ROW order, straight into y, at 10 B per entry:
 //
 //   inspect   sample the column indices (1 in 16) into a histogram, take the K most referenced columns (K = what LDS
-//             holds next to the scan strips: 16 320 fp64 / 36 800 fp32) if they cover >= 15 % of the sample, and
+//             holds next to the scan strips: 16 320 fp64 / 36 736 fp32) if they cover >= 15 % of the sample, and
 //             split A once, stably, into A_hot (values, 16-bit index into the hot list, row offsets) and A_rest (an
 //             ordinary CSR matrix with the remaining entries), each with the source position of every entry (for
 //             update_values).  A_rest gets the regular tiled plan; A_hot the nnz-window row partition of the row-block
@@ -26,7 +26,8 @@
 // like every other plan; bit-reproducible from run to run (no atomics on this path).
 // Chosen by spmv_sliced_build for row-skewed matrices (the ones that get variable-height bins) unless the handle asks for
 // row-range reduces (SPBLAS_GFX950_OPT_BIN_ROW_ALIGN); SPBLAS_GFX950_PB_HOT = 0 / 1 switches it off / forces the attempt,
-// SPBLAS_GFX950_PB_HOT_MIN_PCT the coverage from which the split is taken (default 15).
+// SPBLAS_GFX950_PB_HOT_MIN_PCT the coverage from which the split is taken (default 15).  SPBLAS_GFX950_PB_HOT_GRID (read at
+// inspect, a test hook) sets the workgroups of the multiply: with 1, every wavefront walks nwin / 16 windows.
 #include "common.hpp"
 #include "plan.hpp"
 #include "scan.hpp"
@@ -62,7 +63,7 @@ static constexpr int HOT_LDS = 160 * 1024;
 static constexpr int HOT_HIST = 1024;     // sampled reference counts 0 .. 1022, last bucket = more
 
 template <typename T>
-static constexpr int hot_max_cols() {  // 16 320 fp64, 36 800 fp32 (a multiple of 64 entries; 512 B of row-start bitmaps)
+static constexpr int hot_max_cols() {  // 16 320 fp64, 36 736 fp32 (a multiple of 64 entries; 512 B of row-start bitmaps)
   return (HOT_LDS - HOT_WAVES * HOT_WIN * (int) sizeof(T) - HOT_WAVES * HOT_WIN / 8) / (int) sizeof(T) / 64 * 64;
 }
 
@@ -353,9 +354,14 @@ __device__ __forceinline__ void hot_walk(int64_t w, const int64_t last, const in
     T t[HOT_EPL];
 #pragma unroll
     for (int j = 0; j < HOT_EPL; ++j) {
-      t[j] = cur.v[j] * xs[cur.c[j / 4][j % 4]];  // (pads: 0 * xs[0], past the last row: never part of a sum)
+      t[j] = cur.v[j] * xs[cur.c[j / 4][j % 4]];  // (pads: 0 * xs[0], past the last row: never part of a scanned sum)
     }
     if (rb == re) {  // no row starts here: one wave reduction, the piece of the row that covers the window
+      if (w == last) {  // (the one window that may be partial: its pads are 0 * xs[0], NaN when that x is not finite)
+#pragma unroll
+        for (int j = 0; j < HOT_EPL; ++j)
+          t[j] = wlo + (O) (HOT_EPL * lane + j) < whi ? t[j] : T(0);
+      }
       T v = t[0];
 #pragma unroll
       for (int j = 1; j < HOT_EPL; ++j)
@@ -528,13 +534,21 @@ __global__ __launch_bounds__(256) void hot_cross_rows_kernel(int64_t m_hot, cons
   }
 }
 
+// workgroups of pb_hot_rows_kernel: one per CU as long as each has 16 windows (or what the test hook asked for at inspect)
+static int64_t hot_grid(spblas_gfx950_handle_t h, const spblas_gfx950_plan_s* pl) {
+  if (pl->hot_grid > 0)
+    return pl->hot_grid;
+  const int cus = h->num_cus > 0 ? h->num_cus : 256;
+  const int64_t nwin = pl->hot_plan->nwin;
+  return cdiv(nwin, HOT_WAVES) < cus ? cdiv(nwin, HOT_WAVES) : cus;
+}
+
 template <typename T, typename O>
 static int hot_launch(spblas_gfx950_handle_t h, spblas_gfx950_plan_s* pl, const void* alpha_p, const void* x, void* y) {
   spblas_gfx950_plan_s* hp = pl->hot_plan;
   hipStream_t s = h->stream;
   const T alpha = *static_cast<const T*>(alpha_p);
-  const int cus = h->num_cus > 0 ? h->num_cus : 256;
-  const int64_t grid = cdiv(hp->nwin, HOT_WAVES) < cus ? cdiv(hp->nwin, HOT_WAVES) : cus;
+  const int64_t grid = hot_grid(h, pl);
   const O* rowptr = static_cast<const O*>(hp->rowptr);
   T* head = static_cast<T*>(pl->hot_part);
   T* tail = head + hp->nwin;
@@ -604,6 +618,8 @@ void spmv_hot_free(spblas_gfx950_handle_t h, spblas_gfx950_plan_s* pl) {
   pl->hot_rowptr = pl->rest_rowptr = nullptr;
   pl->hot_k = 0;
   pl->hot_nnz = 0;
+  pl->hot_m = 0;
+  pl->hot_thr = pl->hot_grid = 0;
 }
 
 template <typename T, typename O>
@@ -675,6 +691,8 @@ static int hot_build_typed(spblas_gfx950_handle_t h, spblas_gfx950_plan_s* pl, c
   (void) scan_counts_i32(s, n, pos, partials);
   hipLaunchKernelGGL(hot_colmap_kernel, dim3((unsigned) cdiv(n, 256)), dim3(256), 0, s, n, pos, colmap, pl->hot_cols, colbits);
   pl->hot_k = (int) cols;
+  pl->hot_thr = thr;
+  pl->hot_grid = hot_env("SPBLAS_GFX950_PB_HOT_GRID", 0);
   // stable split of the entries
   hipLaunchKernelGGL(hot_flag_entries_kernel, dim3((unsigned) cdiv(nnz, 256)), dim3(256), 0, s, nnz, colind, colbits, pos);
   long long* total_dev = scan_counts_i32(s, nnz, pos, partials);
@@ -846,6 +864,51 @@ int spmv_hot_update(spblas_gfx950_handle_t h, spblas_gfx950_plan_s* pl, const vo
 }
 
 } // namespace spb
+
+// What the inspect laid out for the hot part (a diagnostic for tests: the counterpart of spblas_gfx950_spmm_plan_blocks).
+extern "C" int spblas_gfx950_plan_hot_layout(spblas_gfx950_handle_t handle, spblas_gfx950_plan_t plan, int64_t counts[8],
+                                             int32_t* hot_cols, int32_t* hot_rows, int64_t* hot_rowptr, int32_t* win_row,
+                                             int32_t* cross_rows) {
+  if (!handle)
+    return SPBLAS_GFX950_STATUS_INVALID_HANDLE;
+  if (!plan || !counts)
+    return SPBLAS_GFX950_STATUS_INVALID_POINTER;
+  if (spb::stream_capturing(handle->stream))
+    return SPBLAS_GFX950_STATUS_NOT_SUPPORTED;
+  for (int i = 0; i < 8; ++i)
+    counts[i] = 0;
+  if (plan->alg != SPBLAS_GFX950_SPMV_SLICED || !plan->hot_plan || !plan->rest_plan)
+    return SPBLAS_GFX950_STATUS_SUCCESS;
+  const int64_t m_hot = plan->hot_m, nwin = plan->hot_plan->nwin;
+  int64_t depth = 0;
+  for (const spblas_gfx950_plan_s* p = plan; p && p->hot_plan && p->rest_plan; p = p->rest_plan)
+    ++depth;
+  const int64_t v[8] = {plan->hot_thr, plan->hot_k, plan->hot_nnz, m_hot, nwin, plan->hot_ncross, spb::hot_grid(handle, plan), depth};
+  for (int i = 0; i < 8; ++i)
+    counts[i] = v[i];
+  hipStream_t s = handle->stream;
+  if (hot_cols)
+    SPB_HIP(hipMemcpyAsync(hot_cols, plan->hot_cols, (size_t) plan->hot_k * 4, hipMemcpyDeviceToHost, s));
+  if (hot_rows)
+    SPB_HIP(hipMemcpyAsync(hot_rows, plan->hot_rows, (size_t) m_hot * 4, hipMemcpyDeviceToHost, s));
+  if (win_row)
+    SPB_HIP(hipMemcpyAsync(win_row, plan->hot_plan->win_row, (size_t) (nwin + 1) * 4, hipMemcpyDeviceToHost, s));
+  if (cross_rows && plan->hot_ncross > 0)
+    SPB_HIP(hipMemcpyAsync(cross_rows, plan->hot_cross, (size_t) plan->hot_ncross * 4, hipMemcpyDeviceToHost, s));
+  std::vector<int32_t> rp32;
+  if (hot_rowptr) {  // (the plan keeps the offsets in the caller's offset type; the diagnostic always hands out 64 bits)
+    if (plan->offset_type == SPBLAS_GFX950_I32) {
+      rp32.resize((size_t) m_hot + 1);
+      SPB_HIP(hipMemcpyAsync(rp32.data(), plan->hot_rowptr, ((size_t) m_hot + 1) * 4, hipMemcpyDeviceToHost, s));
+    } else {
+      SPB_HIP(hipMemcpyAsync(hot_rowptr, plan->hot_rowptr, ((size_t) m_hot + 1) * 8, hipMemcpyDeviceToHost, s));
+    }
+  }
+  SPB_HIP(hipStreamSynchronize(s));
+  for (size_t i = 0; i < rp32.size(); ++i)
+    hot_rowptr[i] = rp32[i];
+  return SPBLAS_GFX950_STATUS_SUCCESS;
+}
 
 // Loads this file's code object (the runtime loads a code object at the first use of one of its kernels: milliseconds
 // that would otherwise fall on the caller's first inspect / compute call -- handle.hip: spblas_gfx950_create).

@@ -50,6 +50,7 @@ def test_null_handle_is_rejected_without_touching_a_gpu():
     assert lib.spblas_gfx950_spmv_t_last(None, None, 8) == _capi.INVALID_HANDLE
     assert lib.spblas_gfx950_sptrsm_last(None, None, 8) == _capi.INVALID_HANDLE
     assert lib.spblas_gfx950_spmm_plan_blocks(None, None, None, None, None, None) == _capi.INVALID_HANDLE
+    assert lib.spblas_gfx950_plan_hot_layout(None, None, None, None, None, None, None, None) == _capi.INVALID_HANDLE
 
 
 def test_package_surface_mirrors_reference_names():
