@@ -8,8 +8,10 @@
 # include/spblas_gfx950.h) plus the HIP runtime for the stream allocator (vendor/gfx950/stream_memory.hpp).
 # The library's sources are the files of spblas-reference_amd/csrc/ listed in _build.SOURCES (multicolor.hip, the multicolour
 # ordering and the symmetric permutation -- spblas_gfx950_multicolor_* / csr_permute_* / permute_vector --, and gauss_seidel.hip,
-# the multicolour Gauss-Seidel / SOR / SSOR sweeps -- spblas_gfx950_gs_* --, among them); the headers it serves are
-# include/spblas/vendor/gfx950/*.hpp (permute_impl.hpp and gauss_seidel_impl.hpp for those calls), all reached through gfx950.hpp.
+# the multicolour Gauss-Seidel / SOR / SSOR sweeps -- spblas_gfx950_gs_* --, and aggregate.hip, the MIS-2 aggregation and the
+# Galerkin coarse matrix -- spblas_gfx950_aggregate_* / coarsen_* --, among them); the headers it serves are
+# include/spblas/vendor/gfx950/*.hpp (permute_impl.hpp, gauss_seidel_impl.hpp and aggregate_impl.hpp for those calls), all
+# reached through gfx950.hpp.
 #
 #   SPBLAS_GFX950_ROOT   checkout of this repository (default: the directory above this file)
 #   SPBLAS_GFX950_LIBDIR directory of libspblas_gfx950.so (default: <root>/spblas-reference_amd/lib, where

@@ -57,6 +57,8 @@ typedef struct spblas_gfx950_trsv_s* spblas_gfx950_trsv_t;
 typedef struct spblas_gfx950_ilu0_s* spblas_gfx950_ilu0_t;
 typedef struct spblas_gfx950_multicolor_s* spblas_gfx950_multicolor_t;
 typedef struct spblas_gfx950_permute_s* spblas_gfx950_permute_t;
+typedef struct spblas_gfx950_aggregate_s* spblas_gfx950_aggregate_t;
+typedef struct spblas_gfx950_coarsen_s* spblas_gfx950_coarsen_t;
 typedef struct spblas_gfx950_gs_s* spblas_gfx950_gs_t;
 
 typedef enum spblas_gfx950_status {
@@ -217,8 +219,8 @@ int spblas_gfx950_spmv_plan_detach(spblas_gfx950_handle_t handle, spblas_gfx950_
 /* A plan carries workspaces (products, partial sums): it must not run on two streams at once.  plan_destroy frees on
  * the handle's current stream, ordered behind the last launch that used the plan on whichever stream that was.  The same
  * holds for EVERY destroy of this header -- spblas_gfx950_sptrsv_destroy, _ilu0_destroy, _gs_destroy, _multicolor_destroy,
- * _csr_permute_destroy, _spgemm_destroy -- and for a symbolic pass that replaces the result a SpGEMM state holds: each owner
- * remembers the stream of its last use, and its arrays are freed (stream-ordered, on the handle's current stream) behind an
+ * _csr_permute_destroy, _aggregate_destroy, _coarsen_destroy, _spgemm_destroy -- and for a symbolic pass that replaces the
+ * result a SpGEMM state holds: each owner remembers the stream of its last use, and its arrays are freed (stream-ordered, on the handle's current stream) behind an
  * event recorded there; the host is not blocked, except that sptrsv_destroy waits for the stream of the last solve before
  * it releases the plan's pinned status word.  Nothing is inserted while the handle's stream is being captured.  Two USES of
  * one owner on different streams are not ordered against each other: that stays the caller's business. */
@@ -802,6 +804,71 @@ int spblas_gfx950_gs_info(spblas_gfx950_gs_t plan, int64_t info[4]);
 int spblas_gfx950_gs_sweep(spblas_gfx950_handle_t handle, spblas_gfx950_gs_t plan, int64_t m, int64_t nnz, int sweeps,
                            int direction, const void* omega, const int32_t* rowptr, const int32_t* colind, const void* values,
                            const void* b, void* x, int value_type);
+
+/* ---- MIS-2 aggregation and the Galerkin coarse matrix  (CSR, int32 indices; no reference counterpart) ------------- */
+/* The two pieces an aggregation-based algebraic multigrid needs next to transpose, SpGEMM and gs_sweep: a rule that groups the
+ * rows into coarse unknowns, and A_c = P^T A P for the piecewise-constant P of that grouping.
+ *   strength      in the value type T: d_i = the FIRST stored diagonal entry of row i, 0 without one; t2 = T(theta * theta),
+ *                 the product taken in double.  A stored (i, j), j != i, is strong iff a_ij * a_ij >= (t2 * |d_i|) * |d_j|,
+ *                 evaluated exactly so (products only).  A NaN on either side makes the entry weak.  theta == 0 makes every
+ *                 stored off-diagonal entry with finite operands strong, explicit zeros included.
+ *   graph         u ~ v iff (u, v) or (v, u) is a strong entry (the pattern need not be symmetric; self loops and repeats
+ *                 count once).
+ *   roots         a maximal independent set at distance 2 (MIS-2; Bell, Dalton, Olson 2012) with the FIXED keys of the
+ *                 colouring above.  One round is four launches on ping-pong arrays, none of which reads what it writes:
+ *                 T1[v] = the largest key of an undecided vertex in {v} + N(v) (0 if none), at every vertex; an undecided v
+ *                 whose key equals the largest T1 in {v} + N(v) becomes a root; every undecided vertex within distance 2 of a
+ *                 root becomes covered (two launches).  The host reads the count of decided vertices after every round.
+ *   determinism   the roots are greedy MIS on the square of the graph in descending key order.  Roots, aggregates and the number
+ *                 of rounds depend on the pattern, the values and theta alone.
+ *   aggregates    the roots are numbered in ascending vertex index.  A root takes its number, a neighbour of a root that root's
+ *                 number; in a second launch every other vertex takes the aggregate of the neighbour of the largest key among
+ *                 those the first launch assigned.  A vertex without a strong neighbour is an aggregate of its own.
+ *   aggregate_create   the inspect: structure check as multicolor_create (STATUS_INVALID_VALUE), transpose, strength, rounds,
+ *                 numbering.  Order of checks: C32 / C64 / F16 / BF16 return STATUS_NOT_SUPPORTED before anything else; then
+ *                 handle, capture (STATUS_NOT_SUPPORTED), pointers, sizes, then STATUS_INVALID_VALUE for m == 0 with nnz != 0, a
+ *                 value type other than F32 / F64, a theta that is negative or not finite.  It synchronises the stream and
+ *                 keeps m + aggregates int32 on the device until aggregate_destroy.
+ *   aggregate_info     info[0] aggregates, [1] rounds, [2] rows of the largest aggregate, [3] of the smallest, [4] aggregates
+ *                 of one row, [5] strong stored entries of A, [6] lanes per row, [7] m.
+ *   aggregate_copy     agg[m] and root[aggregates] (the root row of every aggregate, ascending) into caller-allocated int32
+ *                 device arrays on the stream; either may be NULL.
+ *   aggregate_prolongator   the tentative prolongator P (m x aggregates) as CSR: p_rowptr[m + 1] = 0 .. m, p_colind[m] = agg,
+ *                 p_values[m] = 1 (F32 / F64).  One launch, nothing allocated or synchronised: capturable.  m must be the
+ *                 plan's (STATUS_PLAN_MISMATCH).
+ *   coarsen_create     the inspect of A_c = P^T A P for ANY int32 map agg[m] with entries in [0, n_agg) (a value outside:
+ *                 STATUS_INVALID_VALUE, as for a bad structure; an aggregate without rows gives an empty row of A_c).  Entry p
+ *                 of A is renamed (agg[row], agg[col]); two passes of spblas_gfx950_csr_transpose that carry the source
+ *                 position bring the entries into (I, J, position) order; runs of equal (I, J) collapse to one entry.  The
+ *                 plan keeps c_rowptr[n_agg + 1], c_colind[c_nnz] (ascending, duplicate free), seg_ptr[c_nnz + 1] and
+ *                 map[nnz].  It allocates and synchronises (STATUS_NOT_SUPPORTED inside a capture).  A is m x m.
+ *   coarsen_info       info[0] n_agg, [1] c_nnz -- what to allocate for A_c --, [2] m, [3] nnz.
+ *   coarsen_structure  copies c_rowptr and c_colind into caller-allocated arrays on the stream; capturable.
+ *   coarsen_values     VALUES only: c_values[e] = the sum of a_values[map[q]] for q = seg_ptr[e] .. seg_ptr[e + 1] - 1 in
+ *                 ascending q, which is ascending source position, by plain additions in T that start from the first term: the
+ *                 bits depend on A and agg alone.  One launch, nothing allocated or synchronised, recordable from its first
+ *                 use.  Order of checks: C32 / C64 / F16 / BF16 return STATUS_NOT_SUPPORTED before anything else; then handle,
+ *                 pointers, plan against nnz and c_nnz (STATUS_PLAN_MISMATCH), value type (F32 / F64, else
+ *                 STATUS_INVALID_VALUE), a_values == c_values (STATUS_INVALID_VALUE: no in-place form).
+ * Not offered: smoothed aggregation (a prolongator smoother), classical (Ruge-Stueben) coarsening, a restriction other than
+ * P^T, rectangular or block matrices, weights in P, scaled / conjugated / CSC operands, complex / 16-bit values, int64 indices,
+ * a hierarchy or cycle driver (examples/device_aggregate.cpp shows a two-grid correction). */
+int spblas_gfx950_aggregate_create(spblas_gfx950_handle_t handle, spblas_gfx950_aggregate_t* plan, int64_t m, int64_t nnz,
+                                   const int32_t* rowptr, const int32_t* colind, const void* values, double theta,
+                                   int value_type);
+int spblas_gfx950_aggregate_destroy(spblas_gfx950_handle_t handle, spblas_gfx950_aggregate_t plan);
+int spblas_gfx950_aggregate_info(spblas_gfx950_aggregate_t plan, int64_t info[8]);
+int spblas_gfx950_aggregate_copy(spblas_gfx950_handle_t handle, spblas_gfx950_aggregate_t plan, int32_t* agg, int32_t* root);
+int spblas_gfx950_aggregate_prolongator(spblas_gfx950_handle_t handle, spblas_gfx950_aggregate_t plan, int64_t m,
+                                        int32_t* p_rowptr, int32_t* p_colind, void* p_values, int value_type);
+int spblas_gfx950_coarsen_create(spblas_gfx950_handle_t handle, spblas_gfx950_coarsen_t* plan, int64_t m, int64_t nnz,
+                                 const int32_t* rowptr, const int32_t* colind, const int32_t* agg, int64_t n_agg);
+int spblas_gfx950_coarsen_destroy(spblas_gfx950_handle_t handle, spblas_gfx950_coarsen_t plan);
+int spblas_gfx950_coarsen_info(spblas_gfx950_coarsen_t plan, int64_t info[4]);
+int spblas_gfx950_coarsen_structure(spblas_gfx950_handle_t handle, spblas_gfx950_coarsen_t plan, int32_t* c_rowptr,
+                                    int32_t* c_colind);
+int spblas_gfx950_coarsen_values(spblas_gfx950_handle_t handle, spblas_gfx950_coarsen_t plan, int64_t nnz, const void* a_values,
+                                 int64_t c_nnz, void* c_values, int value_type);
 
 /* ---- scale:  values[i] *= alpha  (algorithms/scale_impl.hpp:13-19) --------------------------- */
 /* In-place scaling of a matrix's value array or of a dense vector (n elements, device memory).  A SLICED

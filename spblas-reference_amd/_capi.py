@@ -153,6 +153,18 @@ PROTOTYPES = [
     ("spblas_gfx950_gs_info", c_int, [c_void_p, ctypes.POINTER(c_i64)]),
     ("spblas_gfx950_gs_sweep", c_int,
      [c_void_p, c_void_p, c_i64, c_i64, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int]),
+    ("spblas_gfx950_aggregate_create", c_int,
+     [c_void_p, ctypes.POINTER(c_void_p), c_i64, c_i64, c_void_p, c_void_p, c_void_p, ctypes.c_double, c_int]),
+    ("spblas_gfx950_aggregate_destroy", c_int, [c_void_p, c_void_p]),
+    ("spblas_gfx950_aggregate_info", c_int, [c_void_p, ctypes.POINTER(c_i64)]),
+    ("spblas_gfx950_aggregate_copy", c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
+    ("spblas_gfx950_aggregate_prolongator", c_int, [c_void_p, c_void_p, c_i64, c_void_p, c_void_p, c_void_p, c_int]),
+    ("spblas_gfx950_coarsen_create", c_int,
+     [c_void_p, ctypes.POINTER(c_void_p), c_i64, c_i64, c_void_p, c_void_p, c_void_p, c_i64]),
+    ("spblas_gfx950_coarsen_destroy", c_int, [c_void_p, c_void_p]),
+    ("spblas_gfx950_coarsen_info", c_int, [c_void_p, ctypes.POINTER(c_i64)]),
+    ("spblas_gfx950_coarsen_structure", c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
+    ("spblas_gfx950_coarsen_values", c_int, [c_void_p, c_void_p, c_i64, c_void_p, c_i64, c_void_p, c_int]),
     ("spblas_gfx950_spgemm_set_addend", c_int, [c_void_p, c_void_p, c_i64, c_void_p, c_void_p]),
     ("spblas_gfx950_spgemm_numeric_addend", c_int,
      [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,

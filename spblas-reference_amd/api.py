@@ -2151,3 +2151,223 @@ def gauss_seidel(info, a, b, x, sweeps=1, omega=1.0, direction="forward"):
                                              _ptr(a.rowptr()), _ptr(a.colind()), _ptr(av), _ptr(b), _ptr(x), vt), what)
     if sweeps > 0:
         _note_write(x)
+
+
+# ---- MIS-2 aggregation and the Galerkin coarse matrix (spblas_gfx950_aggregate_* / coarsen_*; no reference counterpart) ----
+class _AggregatePlan(_NativePlan):
+    """aggregate state: agg and root on the device, what prolongator() reads (spblas_gfx950_aggregate_create)."""
+    _destroy = "spblas_gfx950_aggregate_destroy"
+
+
+def _csr_target(c, shape, nnz, dtype, dev, what, name):
+    """A caller-allocated plain csr_view the call writes into: int32 offsets and columns, values of `dtype`, long enough."""
+    if not isinstance(c, csr_view):
+        raise TypeError(f"{what}: {name} must be a plain csr_view over caller-allocated arrays, got {type(c).__name__}")
+    cv, cr, cc = c.values(), c.rowptr(), c.colind()
+    if not _is_tensor(cv) or not _is_tensor(cr) or not _is_tensor(cc):
+        raise TypeError(f"{what}: {name}'s values, row offsets and columns must be tensors")
+    if cr.dtype != torch.int32 or cc.dtype != torch.int32:
+        raise TypeError(f"{what}: {name} must have int32 row offsets and columns, got {cr.dtype} / {cc.dtype}")
+    if cv.dtype != dtype:
+        raise TypeError(f"{what}: {name}'s values must have the value type {dtype}, got {cv.dtype}")
+    if any(t.device != dev or not t.is_contiguous() for t in (cv, cr, cc)):
+        raise ValueError(f"{what}: {name}'s arrays must be contiguous and live on the operand's device")
+    if cr.numel() < shape[0] + 1 or cc.numel() < nnz or cv.numel() < nnz:
+        raise ValueError(f"{what}: {name}'s arrays must hold {shape[0] + 1} row offsets and {nnz} columns and values")
+    return c
+
+
+class aggregate_t:
+    """Result of aggregate: int32 device tensors `agg` (the aggregate of every row) and `root` (the root row of every
+    aggregate, ascending), `n_agg`, info() and prolongator()."""
+
+    def __init__(self, agg, root, n_agg, info, plan, m):
+        self.agg, self.root, self.n_agg, self._info, self._plan, self._m = agg, root, n_agg, info, plan, m
+
+    def info(self):
+        return dict(self._info)
+
+    def prolongator(self, p):
+        """prolongator(dtype) -> csr_view, or prolongator(p): the tentative prolongator P, m x n_agg, row offsets 0 .. m, columns
+        `agg`, values 1 (float32 / float64).  With a caller-allocated csr_view `p` (m + 1 offsets, m columns and values) it is
+        one launch, nothing allocated or synchronised: recordable in a graph."""
+        what = "prolongator"
+        m, dev = self._m, self.agg.device
+        if isinstance(p, torch.dtype):
+            if p not in (torch.float32, torch.float64):
+                raise TypeError(f"{what}: float32 / float64 values only, got {p}")
+            p = csr_view(torch.empty(m, dtype=p, device=dev), torch.empty(m + 1, dtype=torch.int32, device=dev),
+                         torch.empty(m, dtype=torch.int32, device=dev), (m, self.n_agg), m)
+            ret = True
+        else:
+            ret = False
+            if isinstance(p, csr_view) and _is_tensor(p.values()) and p.values().dtype not in (torch.float32, torch.float64):
+                raise TypeError(f"{what}: float32 / float64 values only, got {p.values().dtype}")
+            _csr_target(p, (m, self.n_agg), m, p.values().dtype if isinstance(p, csr_view) and _is_tensor(p.values()) else None,
+                        dev, what, "p")
+        hd = _Handle.current(dev)
+        vt, _ = _vtype(p.values(), what)
+        check(_capi.lib().spblas_gfx950_aggregate_prolongator(hd.h, self._plan.plan, m, _ptr(p.rowptr()), _ptr(p.colind()),
+                                                              _ptr(p.values()), vt), what)
+        _note_write(p.values(), p.colind())
+        p.update(p.values(), p.rowptr(), p.colind(), (m, self.n_agg), m)
+        return p if ret else None
+
+
+def aggregate(a, theta=0.0):
+    """aggregate(a, theta=0.0) -> aggregate_t: groups the rows of A into aggregates around the roots of a maximal independent set
+    at distance 2 of the strength graph (MIS-2 aggregation after Bell, Dalton and Olson; no reference counterpart).  In A's value
+    type T, with d_i the first stored diagonal entry of row i (0 without one) and t2 = T(theta * theta), a stored off-diagonal
+    a_ij is strong iff a_ij * a_ij >= (t2 * |d_i|) * |d_j|; a NaN on either side makes it weak; theta = 0 keeps every stored
+    off-diagonal entry.  Rows i and j are neighbours iff a_ij or a_ji is strong.  The roots are greedy MIS on the square of that
+    graph in descending order of the fixed keys multicolor_order uses: they, the aggregates and the number of rounds depend on
+    the pattern, the values and theta alone.  A row without a strong neighbour is an aggregate of its own.  `a` is a square plain
+    csr_view (float32 / float64 values, int32 offsets and columns; rows need not be sorted, the pattern need not be symmetric).
+    Inspect-class: synchronises the stream, refused inside a capture."""
+    what = "aggregate"
+    a = _square_csr_operand(a, what)
+    if isinstance(theta, bool) or not isinstance(theta, (int, float)):
+        raise TypeError(f"{what}: theta must be a real number")
+    theta = float(theta)
+    if not (theta >= 0.0) or theta == float("inf"):
+        raise ValueError(f"{what}: theta must be finite and >= 0")
+    dev = a.rowptr().device
+    hd = _Handle.current(dev)
+    m = a.shape()[0]
+    vt, _ = _vtype(a.values(), what)
+    plan = ctypes.c_void_p()
+    st = _capi.lib().spblas_gfx950_aggregate_create(hd.h, ctypes.byref(plan), m, a.size(), _ptr(a.rowptr()), _ptr(a.colind()),
+                                                    _ptr(a.values()), ctypes.c_double(theta), vt)
+    if st == _capi.INVALID_VALUE:
+        raise ValueError(f"{what}: every column must lie inside [0, m) and the row offsets must describe the entries")
+    check(st, what)
+    owner = _AggregatePlan(hd, plan, None)
+    arr = (ctypes.c_int64 * 8)()
+    check(_capi.lib().spblas_gfx950_aggregate_info(plan, arr), "spblas_gfx950_aggregate_info")
+    info = dict(zip(("aggregates", "rounds", "largest", "smallest", "singletons", "strong_entries", "lanes_per_row"), list(arr)))
+    n_agg = info["aggregates"]
+    agg = torch.empty(m, dtype=torch.int32, device=dev)
+    root = torch.empty(n_agg, dtype=torch.int32, device=dev)
+    check(_capi.lib().spblas_gfx950_aggregate_copy(hd.h, plan, _ptr(agg), _ptr(root)), "spblas_gfx950_aggregate_copy")
+    return aggregate_t(agg, root, n_agg, info, owner, m)
+
+
+class _CoarsenPlan(_NativePlan):
+    """coarsen_inspect state: the structure of A_c, the first sorted position of every coarse entry and the source position of
+    every sorted position (spblas_gfx950_coarsen_create)."""
+    _destroy, _info_call = "spblas_gfx950_coarsen_destroy", "spblas_gfx950_coarsen_info"
+    _info_names = ("n_agg", "nnz", "fine_rows", "fine_nnz")
+
+
+def _coarsen_operands(a, agg, n_agg, what):
+    a = _square_csr_operand(a, what)
+    m = a.shape()[0]
+    if not _is_tensor(agg) or agg.dtype != torch.int32:
+        raise TypeError(f"{what}: agg must be an int32 tensor")
+    if agg.device != a.rowptr().device or not agg.is_contiguous() or agg.dim() != 1 or agg.numel() != m:
+        raise ValueError(f"{what}: agg must be a contiguous vector of A's {m} rows on A's device")
+    if isinstance(n_agg, bool) or not isinstance(n_agg, int):
+        raise TypeError(f"{what}: n_agg must be an int")
+    if n_agg < 0 or n_agg >= 2 ** 31 - 1:
+        raise ValueError(f"{what}: n_agg must be a non-negative int32")
+    return a
+
+
+def _coarsen_key(a, agg, n_agg):
+    return (a.rowptr().data_ptr(), a.colind().data_ptr(), tuple(a.shape()), a.size(), agg.data_ptr(), n_agg)
+
+
+def _coarsen_plan(a, agg, n_agg):
+    hd = _Handle.current(a.rowptr().device)
+    plan = ctypes.c_void_p()
+    st = _capi.lib().spblas_gfx950_coarsen_create(hd.h, ctypes.byref(plan), a.shape()[0], a.size(), _ptr(a.rowptr()),
+                                                  _ptr(a.colind()), _ptr(agg), n_agg)
+    if st == _capi.INVALID_VALUE:
+        raise ValueError("coarsen_inspect: every entry of agg must lie inside [0, n_agg), every column of A inside [0, m) and "
+                         "A's row offsets must describe its entries")
+    check(st, "coarsen_inspect")
+    return _CoarsenPlan(hd, plan, _coarsen_key(a, agg, n_agg), (a.rowptr(), a.colind(), agg))
+
+
+def _coarsen_set(info, plan):
+    info.state_ = plan
+    pi = plan.info()
+    info.update_impl_((pi["n_agg"], pi["n_agg"]), pi["nnz"])
+    info.shape, info.nnz = (pi["n_agg"], pi["n_agg"]), pi["nnz"]
+
+
+def coarsen_inspect(*args):
+    """coarsen_inspect(a, agg, n_agg) -> operation_info_t, or coarsen_inspect(info, a, agg, n_agg): the structure of the Galerkin
+    coarse matrix A_c = P^T A P for the piecewise-constant P of ANY int32 map `agg` (m entries in [0, n_agg); ValueError
+    otherwise) -- A need not have been aggregated by aggregate().  Entry p of A becomes (agg[row], agg[col]); equal pairs collapse
+    to one entry of A_c; an aggregate without rows gives an empty row.  info.shape and info.nnz (also result_shape() /
+    result_nnz()) say what to allocate for A_c.  Inspect-class: allocates, synchronises the stream, refused inside a capture."""
+    info, (a, agg, n_agg) = _leading_info(args, 3, "a, agg, n_agg")
+    ret = info is None
+    if ret:
+        info = operation_info_t()
+    a = _coarsen_operands(a, agg, n_agg, "coarsen_inspect")
+    _coarsen_set(info, _coarsen_plan(a, agg, n_agg))
+    return info if ret else None
+
+
+def _coarsen_info_plan(info, what):
+    plan = getattr(info, "state_", None)
+    if not isinstance(plan, _CoarsenPlan):
+        raise TypeError(f"{what}: expected the operation_info_t of coarsen_inspect")
+    return plan
+
+
+def coarsen_structure(info, a_c):
+    """coarsen_structure(info, a_c): writes A_c's row offsets and its ascending, duplicate-free columns into the caller-allocated
+    csr_view `a_c` (info.shape[0] + 1 offsets, info.nnz columns and values).  Copies on the stream: recordable."""
+    what = "coarsen_structure"
+    plan = _coarsen_info_plan(info, what)
+    pi = plan.info()
+    n, cn = pi["n_agg"], pi["nnz"]
+    dev = plan.tensors[0].device
+    if isinstance(a_c, csr_view) and _is_tensor(a_c.values()):
+        _vtype(a_c.values(), what)
+    _csr_target(a_c, (n, n), cn, a_c.values().dtype if isinstance(a_c, csr_view) and _is_tensor(a_c.values()) else None, dev,
+                what, "a_c")
+    hd = _Handle.current(dev)
+    check(_capi.lib().spblas_gfx950_coarsen_structure(hd.h, plan.plan, _ptr(a_c.rowptr()), _ptr(a_c.colind())), what)
+    _note_write(a_c.colind())
+    a_c.update(a_c.values(), a_c.rowptr(), a_c.colind(), (n, n), cn)
+
+
+def _overlap(s, t):
+    """True iff two tensors share bytes."""
+    if s.numel() == 0 or t.numel() == 0 or s.untyped_storage().data_ptr() != t.untyped_storage().data_ptr():
+        return False
+    s0, t0 = s.data_ptr(), t.data_ptr()
+    return s0 < t0 + t.numel() * t.element_size() and t0 < s0 + s.numel() * s.element_size()
+
+
+def coarsen(info, a, a_c):
+    """coarsen(info, a, a_c): the VALUES of A_c = P^T A P: a_c.values[e] = the sum of the values of A's entries that were renamed
+    to coarse entry e, added one after the other in ascending source position, plain additions in A's value type from the first
+    term -- the bits depend on A and agg alone.  One launch, nothing allocated or synchronised: recordable in a graph from its
+    first use, the refresh after A's values changed on a fixed pattern.  `info` is the result of coarsen_inspect; when it was made
+    for other row offset / column arrays than a's, it is replaced by a new inspect of `a` with the same agg and n_agg (which is
+    inspect-class).  a_c's structure is written by coarsen_structure; only its first info.nnz values are written here.  a_c must
+    not alias A's arrays.
+    Not offered: smoothed aggregation, a restriction other than P^T, weights in P, scaled / complex / 16-bit / int64 operands."""
+    what = "coarsen"
+    plan = _coarsen_info_plan(info, what)
+    agg, n_agg = plan.tensors[2], plan.key[-1]
+    a = _coarsen_operands(a, agg, n_agg, what)
+    if plan.key != _coarsen_key(a, agg, n_agg):
+        plan = _coarsen_plan(a, agg, n_agg)  # made for other arrays: analyse now
+        _coarsen_set(info, plan)
+    pi = plan.info()
+    n, cn = pi["n_agg"], pi["nnz"]
+    av = a.values()
+    _csr_target(a_c, (n, n), cn, av.dtype, av.device, what, "a_c")
+    cv = a_c.values()
+    if any(_overlap(x, y) for x in (cv, a_c.rowptr(), a_c.colind()) for y in (av, a.rowptr(), a.colind(), agg)):
+        raise ValueError(f"{what}: a_c must have arrays of its own (there is no in-place form)")
+    hd = _Handle.current(av.device)
+    vt, _ = _vtype(av, what)
+    check(_capi.lib().spblas_gfx950_coarsen_values(hd.h, plan.plan, a.size(), _ptr(av), cn, _ptr(cv), vt), what)
+    _note_write(cv)

@@ -142,7 +142,7 @@ class dev_temps {
   }
 
  private:
-  static constexpr int kMax = 12;
+  static constexpr int kMax = 20;
   hipStream_t s_;
   void* p_[kMax];
   int n_ = 0;

@@ -26,6 +26,7 @@ void preload_sptrsv_sweeps();
 void preload_ilu0();
 void preload_multicolor();
 void preload_gauss_seidel();
+void preload_aggregate();
 void preload_multigpu();
 } // namespace spb
 
@@ -92,6 +93,7 @@ int spblas_gfx950_create(spblas_gfx950_handle_t* handle, void* stream) {
       spb::preload_ilu0();
       spb::preload_multicolor();
       spb::preload_gauss_seidel();
+      spb::preload_aggregate();
       spb::preload_multigpu();
     });
   return SPBLAS_GFX950_STATUS_SUCCESS;

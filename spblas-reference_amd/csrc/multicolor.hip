@@ -35,6 +35,7 @@
 #include "complex_api.hpp"
 #include "csr_inspect.hpp"
 #include "lowp_api.hpp"
+#include "mc_key.hpp"
 #include "scan.hpp"
 
 #include <algorithm>
@@ -63,16 +64,7 @@ struct spblas_gfx950_permute_s {
 
 namespace spb {
 
-__device__ __forceinline__ uint64_t mc_key(int v) {
-  uint32_t x = ((uint32_t) v + 1u) * 0x9E3779B1u;
-  x ^= x >> 16;
-  x *= 0x85EBCA6Bu;
-  x ^= x >> 13;
-  x *= 0xC2B2AE35u;
-  x ^= x >> 16;
-  return ((uint64_t) x << 32) | (uint32_t) v;
-}
-
+// (mc_key: mc_key.hpp, shared with aggregate.hip)
 struct mc_args {
   const int32_t *rowptr, *colind;      // A
   const int32_t *t_rowptr, *t_colind;  // the pattern of A^T
