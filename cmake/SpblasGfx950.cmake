@@ -9,8 +9,9 @@
 # The library's sources are the files of spblas-reference_amd/csrc/ listed in _build.SOURCES (multicolor.hip, the multicolour
 # ordering and the symmetric permutation -- spblas_gfx950_multicolor_* / csr_permute_* / permute_vector --, and gauss_seidel.hip,
 # the multicolour Gauss-Seidel / SOR / SSOR sweeps -- spblas_gfx950_gs_* --, and aggregate.hip, the MIS-2 aggregation and the
-# Galerkin coarse matrix -- spblas_gfx950_aggregate_* / coarsen_* --, among them); the headers it serves are
-# include/spblas/vendor/gfx950/*.hpp (permute_impl.hpp, gauss_seidel_impl.hpp and aggregate_impl.hpp for those calls), all
+# Galerkin coarse matrix -- spblas_gfx950_aggregate_* / coarsen_* --, and smooth.hip, the smoothed prolongator --
+# spblas_gfx950_smooth_* --, among them); the headers it serves are include/spblas/vendor/gfx950/*.hpp (permute_impl.hpp,
+# gauss_seidel_impl.hpp, aggregate_impl.hpp and smooth_impl.hpp for those calls), all
 # reached through gfx950.hpp.
 #
 #   SPBLAS_GFX950_ROOT   checkout of this repository (default: the directory above this file)

@@ -59,6 +59,7 @@ typedef struct spblas_gfx950_multicolor_s* spblas_gfx950_multicolor_t;
 typedef struct spblas_gfx950_permute_s* spblas_gfx950_permute_t;
 typedef struct spblas_gfx950_aggregate_s* spblas_gfx950_aggregate_t;
 typedef struct spblas_gfx950_coarsen_s* spblas_gfx950_coarsen_t;
+typedef struct spblas_gfx950_smooth_s* spblas_gfx950_smooth_t;
 typedef struct spblas_gfx950_gs_s* spblas_gfx950_gs_t;
 
 typedef enum spblas_gfx950_status {
@@ -219,7 +220,7 @@ int spblas_gfx950_spmv_plan_detach(spblas_gfx950_handle_t handle, spblas_gfx950_
 /* A plan carries workspaces (products, partial sums): it must not run on two streams at once.  plan_destroy frees on
  * the handle's current stream, ordered behind the last launch that used the plan on whichever stream that was.  The same
  * holds for EVERY destroy of this header -- spblas_gfx950_sptrsv_destroy, _ilu0_destroy, _gs_destroy, _multicolor_destroy,
- * _csr_permute_destroy, _aggregate_destroy, _coarsen_destroy, _spgemm_destroy -- and for a symbolic pass that replaces the
+ * _csr_permute_destroy, _aggregate_destroy, _coarsen_destroy, _smooth_destroy, _spgemm_destroy -- and for a symbolic pass that replaces the
  * result a SpGEMM state holds: each owner remembers the stream of its last use, and its arrays are freed (stream-ordered, on the handle's current stream) behind an
  * event recorded there; the host is not blocked, except that sptrsv_destroy waits for the stream of the last solve before
  * it releases the plan's pinned status word.  Nothing is inserted while the handle's stream is being captured.  Two USES of
@@ -850,9 +851,43 @@ int spblas_gfx950_gs_sweep(spblas_gfx950_handle_t handle, spblas_gfx950_gs_t pla
  *                 use.  Order of checks: C32 / C64 / F16 / BF16 return STATUS_NOT_SUPPORTED before anything else; then handle,
  *                 pointers, plan against nnz and c_nnz (STATUS_PLAN_MISMATCH), value type (F32 / F64, else
  *                 STATUS_INVALID_VALUE), a_values == c_values (STATUS_INVALID_VALUE: no in-place form).
- * Not offered: smoothed aggregation (a prolongator smoother), classical (Ruge-Stueben) coarsening, a restriction other than
+ *   smooth_*           the smoothed prolongator P = (I - omega D_F^-1 A_F) T of smoothed aggregation (Vanek, Mandel, Brezina
+ *                 1996): T is the piecewise-constant prolongator of ANY int32 map agg[m] into [0, n_agg), A_F is A with its weak
+ *                 off-diagonal entries (the strength rule above) removed and added to the diagonal, D_F its diagonal.
+ *   smooth_create      the inspect, value-free.  Row i of P holds one entry for every distinct aggregate among {agg[i]} and
+ *                 {agg[j] : (i, j) stored in A}, columns ascending; a weak or cancelling contribution leaves an explicit zero.
+ *                 An extended list of nnz + m entries -- row i gives (agg[i], payload -1) first, then (agg[col], payload p) for
+ *                 its entries -- goes through one pair of spblas_gfx950_csr_transpose over the m x n_agg matrix, there and back:
+ *                 (row, J, position) order with the own-aggregate marker first in its run; head flags and one scan give the
+ *                 tables.  Checks as coarsen_create, in its order (agg and the structure before anything indexes with them);
+ *                 STATUS_INVALID_SIZE when nnz + m does not fit int32.  It allocates and synchronises (STATUS_NOT_SUPPORTED
+ *                 inside a capture).  The plan keeps p_rowptr[m + 1], p_colind[p_nnz], seg_ptr[p_nnz + 1], map[nnz + m] and
+ *                 one work array of m 8-byte slots (d) the value pass rewrites: ONE PLAN SERVES ONE STREAM AT A TIME.
+ *   smooth_info        info[0] n_agg, [1] p_nnz -- what to allocate for P (m x n_agg) --, [2] m, [3] nnz.
+ *   smooth_structure   copies p_rowptr and p_colind into caller-allocated arrays on the stream; capturable.
+ *   smooth_values      VALUES only, fixed to the bit in the value type T (F32 / F64):
+ *                   d_i      the first stored diagonal entry of row i, 0 without one; t2 = T(theta * theta)
+ *                   strong   a stored (i, j), j != i, with a * a >= (t2 * |d_i|) * |d_j|, exactly as for aggregate_create
+ *                   dF_i     T(0) plus, in ascending stored position, every entry of row i that has j == i (repeats
+ *                            included) or is a weak off-diagonal entry; plain additions
+ *                   row i    is smoothed iff dF_i is finite and non-zero: s_i = T(omega) / dF_i (the IEEE quotient) and
+ *                            base_i = T(1) - T(omega); otherwise s_i = 0 and base_i = 1 (the row of T; an empty row is a
+ *                            single 1)
+ *                   P(i, J)  fma(-s_i, acc, b) -- one fused multiply-add --, acc = T(0) plus the strong entries of row i with
+ *                            agg[j] == J in ascending position by plain additions, b = base_i if J == agg[i], else 0
+ *                 theta == 0 makes every finite off-diagonal entry strong; omega == 0 gives T on P's pattern.  What overflows
+ *                 past s_i is the caller's.  The bits depend on A, agg, omega and theta alone.  Two launches (d, then one team
+ *                 of lanes per fine row that stages the row in LDS), nothing allocated or synchronised, recordable from its
+ *                 first use.  omega points at one host scalar of the value type, read during the call.  rowptr / colind are
+ *                 the arrays smooth_create saw.  Order of checks: C32 / C64 / F16 / BF16 return STATUS_NOT_SUPPORTED before
+ *                 anything else; then handle, pointers, plan against m, nnz and p_nnz (STATUS_PLAN_MISMATCH), value type
+ *                 (F32 / F64, else STATUS_INVALID_VALUE), omega not finite or theta negative or not finite
+ *                 (STATUS_INVALID_VALUE), a_values == p_values (STATUS_INVALID_VALUE: no in-place form).
+ * Not offered: an estimate of the spectral radius of D^-1 A (the caller supplies omega), a fused P^T A P for a general P (two
+ * SpGEMMs do it), classical (Ruge-Stueben) coarsening, a restriction other than
  * P^T, rectangular or block matrices, weights in P, scaled / conjugated / CSC operands, complex / 16-bit values, int64 indices,
- * a hierarchy or cycle driver (examples/device_aggregate.cpp shows a two-grid correction). */
+ * a hierarchy or cycle driver (examples/device_aggregate.cpp and examples/device_smoothed_aggregation.cpp show a two-grid
+ * correction). */
 int spblas_gfx950_aggregate_create(spblas_gfx950_handle_t handle, spblas_gfx950_aggregate_t* plan, int64_t m, int64_t nnz,
                                    const int32_t* rowptr, const int32_t* colind, const void* values, double theta,
                                    int value_type);
@@ -869,6 +904,15 @@ int spblas_gfx950_coarsen_structure(spblas_gfx950_handle_t handle, spblas_gfx950
                                     int32_t* c_colind);
 int spblas_gfx950_coarsen_values(spblas_gfx950_handle_t handle, spblas_gfx950_coarsen_t plan, int64_t nnz, const void* a_values,
                                  int64_t c_nnz, void* c_values, int value_type);
+int spblas_gfx950_smooth_create(spblas_gfx950_handle_t handle, spblas_gfx950_smooth_t* plan, int64_t m, int64_t nnz,
+                                const int32_t* rowptr, const int32_t* colind, const int32_t* agg, int64_t n_agg);
+int spblas_gfx950_smooth_destroy(spblas_gfx950_handle_t handle, spblas_gfx950_smooth_t plan);
+int spblas_gfx950_smooth_info(spblas_gfx950_smooth_t plan, int64_t info[4]);
+int spblas_gfx950_smooth_structure(spblas_gfx950_handle_t handle, spblas_gfx950_smooth_t plan, int32_t* p_rowptr,
+                                   int32_t* p_colind);
+int spblas_gfx950_smooth_values(spblas_gfx950_handle_t handle, spblas_gfx950_smooth_t plan, int64_t m, int64_t nnz,
+                                const int32_t* rowptr, const int32_t* colind, const void* a_values, const void* omega,
+                                double theta, int64_t p_nnz, void* p_values, int value_type);
 
 /* ---- scale:  values[i] *= alpha  (algorithms/scale_impl.hpp:13-19) --------------------------- */
 /* In-place scaling of a matrix's value array or of a dense vector (n elements, device memory).  A SLICED

@@ -1319,6 +1319,59 @@ void coarsen(operation_info_t& info, const csr_view<T, std::int32_t, std::int32_
   }
   st.template values<T>(a.values().data(), a_c.values().data());
 }
+
+// ---- the smoothed prolongator of smoothed aggregation (spblas_gfx950_smooth_*; no reference counterpart) ----------------------
+// P = (I - omega D_F^-1 A_F) T for the piecewise-constant T of ANY int32 map agg into [0, n_agg): A_F is A with its weak
+// off-diagonal entries (the strength rule above) removed and added to the diagonal, D_F its diagonal.  smooth_prolongator_inspect
+// sizes P (value-free), smooth_prolongator_structure writes its row offsets and ascending columns, smooth_prolongator writes
+// VALUES only, fixed to the bit (include/spblas_gfx950.h, smooth_values): two launches, capturable.  One info serves one stream
+// at a time.
+// (smooth_prolongator_info_t {rows, columns, nnz} comes with the backend calls.)
+template <typename T>
+smooth_prolongator_info_t smooth_prolongator_inspect(operation_info_t& info, const csr_view<T, std::int32_t, std::int32_t>& a,
+                                                     std::type_identity_t<std::span<const std::int32_t>> agg,
+                                                     std::int64_t n_agg) {
+  static_assert(std::is_same_v<T, float> || std::is_same_v<T, double>, "smooth_prolongator_inspect: float / double values only");
+  if (a.shape()[0] != a.shape()[1] || agg.size() != static_cast<std::size_t>(a.shape()[0])) {
+    throw std::invalid_argument("smooth_prolongator_inspect: matrix dimensions are incompatible.");
+  }
+  auto& st = __gfx950::state_of<__gfx950::smooth_state_t>(info);
+  st.inspect(a.shape()[0], a.size(), a.rowptr().data(), a.colind().data(), agg.data(), n_agg);
+  info.update_impl_({static_cast<index_t>(a.shape()[0]), static_cast<index_t>(n_agg)}, st.p_nnz());
+  return smooth_prolongator_info_t{st.fine_rows(), st.columns(), st.p_nnz()};
+}
+template <typename T>
+void smooth_prolongator_structure(operation_info_t& info, const csr_view<T, std::int32_t, std::int32_t>& p) {
+  auto& st = __gfx950::state_of<__gfx950::smooth_state_t>(info);
+  if (!st.ready()) {
+    throw std::invalid_argument("smooth_prolongator_structure: info must come from smooth_prolongator_inspect.");
+  }
+  if (p.rowptr().size() < static_cast<std::size_t>(st.fine_rows()) + 1 ||
+      p.colind().size() < static_cast<std::size_t>(st.p_nnz())) {
+    throw std::invalid_argument("smooth_prolongator_structure: p must hold m + 1 row offsets and nnz(P) columns.");
+  }
+  st.structure(p.rowptr().data(), p.colind().data());
+}
+// With an info made for other row offset / column arrays the same aggregation is inspected again first (inspect-class).
+template <typename T>
+void smooth_prolongator(operation_info_t& info, const csr_view<T, std::int32_t, std::int32_t>& a,
+                        const csr_view<T, std::int32_t, std::int32_t>& p, std::type_identity_t<T> omega, double theta = 0.0) {
+  static_assert(std::is_same_v<T, float> || std::is_same_v<T, double>, "smooth_prolongator: float / double values only");
+  auto& st = __gfx950::state_of<__gfx950::smooth_state_t>(info);
+  if (!st.ready()) {
+    throw std::invalid_argument("smooth_prolongator: info must come from smooth_prolongator_inspect.");
+  }
+  if (a.shape()[0] != a.shape()[1] || a.shape()[0] != st.fine_rows() || static_cast<std::int64_t>(a.size()) != st.fine_nnz()) {
+    throw std::invalid_argument("smooth_prolongator: matrix dimensions are incompatible.");
+  }
+  if (!st.matches(a.rowptr().data(), a.colind().data())) {
+    st.reinspect(a.rowptr().data(), a.colind().data());
+  }
+  if (p.values().size() < static_cast<std::size_t>(st.p_nnz())) {
+    throw std::invalid_argument("smooth_prolongator: p must hold nnz(P) values.");
+  }
+  st.template values<T>(a.rowptr().data(), a.colind().data(), a.values().data(), omega, theta, p.values().data());
+}
 } // namespace gfx950
 
 } // namespace spblas

@@ -27,3 +27,9 @@ from .api import (  # noqa: F401
 aggregate, aggregate_t = api.aggregate, api.aggregate_t  # noqa: F821
 coarsen, coarsen_inspect, coarsen_structure = api.coarsen, api.coarsen_inspect, api.coarsen_structure  # noqa: F821
 AGGREGATION_EXPORTS = ("aggregate", "aggregate_t", "coarsen", "coarsen_inspect", "coarsen_structure")
+
+# The smoothed prolongator: bound and tabled in the same way (tests/smooth_util.py: STREAM_CASES, proved by
+# tests/test_smooth_cpu.py, run by tests/test_gpu_smooth_stream.py).
+smooth_prolongator, smooth_prolongator_inspect, smooth_prolongator_structure = (  # noqa: F821
+    api.smooth_prolongator, api.smooth_prolongator_inspect, api.smooth_prolongator_structure)
+SMOOTH_EXPORTS = ("smooth_prolongator", "smooth_prolongator_inspect", "smooth_prolongator_structure")

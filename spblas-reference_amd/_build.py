@@ -11,7 +11,7 @@ _ROOT = os.path.dirname(_PKG)
 CSRC = os.path.join(_PKG, "csrc")
 LIBDIR = os.path.join(_PKG, "lib")
 LIBPATH = os.path.join(LIBDIR, "libspblas_gfx950.so")
-SOURCES = ["handle.hip", "spmv.hip", "spmv_sliced.hip", "spmv_hot.hip", "spmm.hip", "spgemm.hip", "transpose.hip", "sptrsv.hip", "sptrsm.hip", "sptrsv_sweeps.hip", "ilu0.hip", "multicolor.hip", "gauss_seidel.hip", "aggregate.hip", "multigpu.hip",
+SOURCES = ["handle.hip", "spmv.hip", "spmv_sliced.hip", "spmv_hot.hip", "spmm.hip", "spgemm.hip", "transpose.hip", "sptrsv.hip", "sptrsm.hip", "sptrsv_sweeps.hip", "ilu0.hip", "multicolor.hip", "gauss_seidel.hip", "aggregate.hip", "smooth.hip", "multigpu.hip",
            "complex.hip", "lowp.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-munsafe-fp-atomics",
          "-Wall", "-Wno-unused-function", "-I", os.path.join(_ROOT, "include"), "-I", CSRC]
@@ -105,7 +105,7 @@ def build_rccl_test(force=False):
     return RCCL_TEST_BIN
 
 
-EXAMPLES = ["device_spmv", "device_spgemm", "device_sptrsv", "device_sptrsm", "device_ilu0", "device_sptrsv_sweeps", "device_ilu0_sweeps", "device_multicolor", "device_gauss_seidel", "device_aggregate"]
+EXAMPLES = ["device_spmv", "device_spgemm", "device_sptrsv", "device_sptrsm", "device_ilu0", "device_sptrsv_sweeps", "device_ilu0_sweeps", "device_multicolor", "device_gauss_seidel", "device_aggregate", "device_smoothed_aggregation"]
 
 
 def build_examples(force=False):

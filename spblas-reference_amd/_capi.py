@@ -165,6 +165,13 @@ PROTOTYPES = [
     ("spblas_gfx950_coarsen_info", c_int, [c_void_p, ctypes.POINTER(c_i64)]),
     ("spblas_gfx950_coarsen_structure", c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
     ("spblas_gfx950_coarsen_values", c_int, [c_void_p, c_void_p, c_i64, c_void_p, c_i64, c_void_p, c_int]),
+    ("spblas_gfx950_smooth_create", c_int,
+     [c_void_p, ctypes.POINTER(c_void_p), c_i64, c_i64, c_void_p, c_void_p, c_void_p, c_i64]),
+    ("spblas_gfx950_smooth_destroy", c_int, [c_void_p, c_void_p]),
+    ("spblas_gfx950_smooth_info", c_int, [c_void_p, ctypes.POINTER(c_i64)]),
+    ("spblas_gfx950_smooth_structure", c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
+    ("spblas_gfx950_smooth_values", c_int,
+     [c_void_p, c_void_p, c_i64, c_i64, c_void_p, c_void_p, c_void_p, c_void_p, ctypes.c_double, c_i64, c_void_p, c_int]),
     ("spblas_gfx950_spgemm_set_addend", c_int, [c_void_p, c_void_p, c_i64, c_void_p, c_void_p]),
     ("spblas_gfx950_spgemm_numeric_addend", c_int,
      [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,

@@ -2352,7 +2352,8 @@ def coarsen(info, a, a_c):
     for other row offset / column arrays than a's, it is replaced by a new inspect of `a` with the same agg and n_agg (which is
     inspect-class).  a_c's structure is written by coarsen_structure; only its first info.nnz values are written here.  a_c must
     not alias A's arrays.
-    Not offered: smoothed aggregation, a restriction other than P^T, weights in P, scaled / complex / 16-bit / int64 operands."""
+    Not offered: a restriction other than P^T, weights in P (smooth_prolongator makes the smoothed P; A_c for it is two
+    SpGEMMs), scaled / complex / 16-bit / int64 operands."""
     what = "coarsen"
     plan = _coarsen_info_plan(info, what)
     agg, n_agg = plan.tensors[2], plan.key[-1]
@@ -2371,3 +2372,118 @@ def coarsen(info, a, a_c):
     vt, _ = _vtype(av, what)
     check(_capi.lib().spblas_gfx950_coarsen_values(hd.h, plan.plan, a.size(), _ptr(av), cn, _ptr(cv), vt), what)
     _note_write(cv)
+
+
+# ---- the smoothed prolongator of smoothed aggregation (spblas_gfx950_smooth_*; no reference counterpart) ----
+class _SmoothPlan(_NativePlan):
+    """smooth_prolongator_inspect state: the structure of P, the first sorted position of every entry of P, the source position
+    of every sorted position and the work array of the value pass (spblas_gfx950_smooth_create)."""
+    _destroy, _info_call = "spblas_gfx950_smooth_destroy", "spblas_gfx950_smooth_info"
+    _info_names = ("n_agg", "nnz", "fine_rows", "fine_nnz")
+
+
+def _smooth_plan(a, agg, n_agg):
+    hd = _Handle.current(a.rowptr().device)
+    plan = ctypes.c_void_p()
+    st = _capi.lib().spblas_gfx950_smooth_create(hd.h, ctypes.byref(plan), a.shape()[0], a.size(), _ptr(a.rowptr()),
+                                                 _ptr(a.colind()), _ptr(agg), n_agg)
+    if st == _capi.INVALID_VALUE:
+        raise ValueError("smooth_prolongator_inspect: every entry of agg must lie inside [0, n_agg), every column of A inside "
+                         "[0, m) and A's row offsets must describe its entries")
+    check(st, "smooth_prolongator_inspect")
+    return _SmoothPlan(hd, plan, _coarsen_key(a, agg, n_agg), (a.rowptr(), a.colind(), agg))
+
+
+def _smooth_set(info, plan):
+    info.state_ = plan
+    pi = plan.info()
+    info.update_impl_((pi["fine_rows"], pi["n_agg"]), pi["nnz"])
+    info.shape, info.nnz = (pi["fine_rows"], pi["n_agg"]), pi["nnz"]
+
+
+def smooth_prolongator_inspect(*args):
+    """smooth_prolongator_inspect(a, agg, n_agg) -> operation_info_t, or smooth_prolongator_inspect(info, a, agg, n_agg): the
+    structure of the smoothed prolongator P = (I - omega D_F^-1 A_F) T for the piecewise-constant T of ANY int32 map `agg` (m
+    entries in [0, n_agg); ValueError otherwise).  Row i of P holds one entry for every distinct aggregate among agg[i] and the
+    agg[j] of row i's stored entries, columns ascending -- whatever the values are: a weak or cancelling contribution leaves an
+    explicit zero.  info.shape = (m, n_agg) and info.nnz (also result_shape() / result_nnz()) say what to allocate for P.
+    Value-free.  Inspect-class: allocates, synchronises the stream, refused inside a capture.  One info serves one stream at a
+    time (it holds a work array the value pass rewrites)."""
+    info, (a, agg, n_agg) = _leading_info(args, 3, "a, agg, n_agg")
+    ret = info is None
+    if ret:
+        info = operation_info_t()
+    a = _coarsen_operands(a, agg, n_agg, "smooth_prolongator_inspect")
+    _smooth_set(info, _smooth_plan(a, agg, n_agg))
+    return info if ret else None
+
+
+def _smooth_info_plan(info, what):
+    plan = getattr(info, "state_", None)
+    if not isinstance(plan, _SmoothPlan):
+        raise TypeError(f"{what}: expected the operation_info_t of smooth_prolongator_inspect")
+    return plan
+
+
+def smooth_prolongator_structure(info, p):
+    """smooth_prolongator_structure(info, p): writes P's row offsets and its ascending, duplicate-free columns into the
+    caller-allocated csr_view `p` (info.shape[0] + 1 offsets, info.nnz columns and values).  Copies on the stream: recordable."""
+    what = "smooth_prolongator_structure"
+    plan = _smooth_info_plan(info, what)
+    pi = plan.info()
+    shape, pn = (pi["fine_rows"], pi["n_agg"]), pi["nnz"]
+    dev = plan.tensors[0].device
+    if isinstance(p, csr_view) and _is_tensor(p.values()):
+        _vtype(p.values(), what)
+    _csr_target(p, shape, pn, p.values().dtype if isinstance(p, csr_view) and _is_tensor(p.values()) else None, dev, what, "p")
+    hd = _Handle.current(dev)
+    check(_capi.lib().spblas_gfx950_smooth_structure(hd.h, plan.plan, _ptr(p.rowptr()), _ptr(p.colind())), what)
+    _note_write(p.colind())
+    p.update(p.values(), p.rowptr(), p.colind(), shape, pn)
+
+
+def smooth_prolongator(info, a, p, omega, theta=0.0):
+    """smooth_prolongator(info, a, p, omega, theta=0.0): the VALUES of P = (I - omega D_F^-1 A_F) T, fixed to the bit in A's value
+    type T.  With the strength rule of aggregate (d_i the first stored diagonal entry, t2 = T(theta * theta), a_ij strong iff
+    j != i and a_ij * a_ij >= (t2 * |d_i|) * |d_j|):  dF_i = T(0) plus, in ascending stored position, every entry of row i on
+    the diagonal (repeats included) or weak;  when dF_i is finite and non-zero, s_i = T(omega) / dF_i and base_i = T(1) -
+    T(omega), else s_i = 0 and base_i = 1 (the row of T);  P(i, J) = fma(-s_i, acc, b) with acc = T(0) plus the strong entries
+    of row i whose column lies in aggregate J, in ascending position, and b = base_i if J == agg[i] else 0.  theta = 0 makes
+    every finite off-diagonal entry strong; omega = 0 gives T on P's pattern.  The bits depend on A, agg, omega and theta alone.
+    Two launches, nothing allocated or synchronised: recordable in a graph from its first use, the refresh after A's values
+    changed on a fixed pattern.  `info` is the result of smooth_prolongator_inspect; when it was made for other row offset /
+    column arrays than a's, it is replaced by a new inspect of `a` with the same agg and n_agg (which is inspect-class).  p's
+    structure is written by smooth_prolongator_structure; only its first info.nnz values are written here.  p must not alias
+    A's arrays.  omega must be finite, theta finite and >= 0.
+    Not offered: an estimate of the spectral radius of D^-1 A (the caller supplies omega), a hierarchy or cycle driver, a fused
+    P^T A P for this P (transpose and two multiply calls do it), scaled / complex / 16-bit / int64 / CSC operands."""
+    what = "smooth_prolongator"
+    plan = _smooth_info_plan(info, what)
+    agg, n_agg = plan.tensors[2], plan.key[-1]
+    a = _coarsen_operands(a, agg, n_agg, what)
+    for name, x in (("omega", omega), ("theta", theta)):
+        if isinstance(x, bool) or not isinstance(x, (int, float)):
+            raise TypeError(f"{what}: {name} must be a real number")
+    omega, theta = float(omega), float(theta)
+    if omega != omega or omega in (float("inf"), float("-inf")):
+        raise ValueError(f"{what}: omega must be finite")
+    if not (theta >= 0.0) or theta == float("inf"):
+        raise ValueError(f"{what}: theta must be finite and >= 0")
+    if plan.key != _coarsen_key(a, agg, n_agg):
+        plan = _smooth_plan(a, agg, n_agg)  # made for other arrays: analyse now
+        _smooth_set(info, plan)
+    pi = plan.info()
+    shape, pn = (pi["fine_rows"], pi["n_agg"]), pi["nnz"]
+    av = a.values()
+    _csr_target(p, shape, pn, av.dtype, av.device, what, "p")
+    pv = p.values()
+    if any(_overlap(x, y) for x in (pv, p.rowptr(), p.colind()) for y in (av, a.rowptr(), a.colind(), agg)):
+        raise ValueError(f"{what}: p must have arrays of its own (there is no in-place form)")
+    hd = _Handle.current(av.device)
+    vt, ctype = _vtype(av, what)
+    w = ctype(omega)
+    if not np.isfinite(w.value):
+        raise ValueError(f"{what}: omega must be finite in A's value type")
+    check(_capi.lib().spblas_gfx950_smooth_values(hd.h, plan.plan, a.shape()[0], a.size(), _ptr(a.rowptr()), _ptr(a.colind()),
+                                                  _ptr(av), ctypes.byref(w), ctypes.c_double(theta), pn, _ptr(pv), vt), what)
+    _note_write(pv)

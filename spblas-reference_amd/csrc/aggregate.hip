@@ -34,6 +34,7 @@
 //   as the payload (as in csr_permute_create).  Runs of equal (I, J) collapse: head flags, one scan, seg_ptr / c_colind / c_rowptr.
 // coarsen_values  c[e] = a[map[seg_ptr[e]]] + a[map[seg_ptr[e] + 1]] + ... in ascending sorted position = ascending source
 //   position, plain additions in T from the first term: the bits depend on A and agg alone.  One launch.
+#include "aggregate_kernels.hpp"
 #include "common.hpp"
 #include "complex_api.hpp"
 #include "csr_inspect.hpp"
@@ -45,8 +46,6 @@
 #include <cmath>
 #include <cstdint>
 #include <new>
-
-#define AG_THREADS 256
 
 struct spblas_gfx950_aggregate_s {
   int64_t m = 0, nnz = 0;
@@ -87,50 +86,11 @@ __device__ __forceinline__ void ag_neighbours(const ag_graph& g, int v, int t, F
       f(g.t_colind[q]);
 }
 
-template <int G, typename V>
-__device__ __forceinline__ V ag_team_max(V x) {
-#pragma unroll
-  for (int o = G >> 1; o > 0; o >>= 1) {
-    const V y = __shfl_xor(x, o, SPB_WAVE);
-    x = y > x ? y : x;
-  }
-  return x;
-}
-
-// the vertex of a thread's team, or -1 past the end (uniform inside a team: the shuffles read active lanes only)
-template <int G>
-__device__ __forceinline__ int ag_vertex(int m) {
-  const int64_t v = (int64_t) blockIdx.x * (AG_THREADS / G) + (int) threadIdx.x / G;
-  return v < m ? (int) v : -1;
-}
-
 // counter += the lanes of this wavefront with `one` set; every lane of the wavefront calls it
 __device__ __forceinline__ void ag_count(unsigned* counter, bool one) {
   const unsigned long long b = __ballot(one);
   if ((threadIdx.x & 63) == 0 && b != 0ull)
     atomicAdd(counter, (unsigned) __popcll(b));
-}
-
-__device__ __forceinline__ float ag_abs(float x) { return __builtin_fabsf(x); }
-__device__ __forceinline__ double ag_abs(double x) { return __builtin_fabs(x); }
-
-// d[v] = the first stored diagonal entry of row v, 0 without one
-template <typename T, int G>
-__global__ __launch_bounds__(AG_THREADS) void ag_diag_kernel(int m, const int32_t* __restrict__ rowptr,
-                                                             const int32_t* __restrict__ colind, const T* __restrict__ values,
-                                                             T* __restrict__ d) {
-  const int t = (int) threadIdx.x % G, v = ag_vertex<G>(m);
-  if (v < 0)
-    return;
-  int first = INT32_MAX;
-  for (int p = rowptr[v] + t, p1 = rowptr[v + 1]; p < p1; p += G)
-    if (colind[p] == v) {
-      first = p;
-      break;
-    }
-  first = -ag_team_max<G>(-first);
-  if (t == 0)
-    d[v] = first != INT32_MAX ? values[first] : T(0);
 }
 
 // strong[p] of every entry of A; counters[5] += the strong ones
@@ -146,7 +106,7 @@ __global__ __launch_bounds__(AG_THREADS) void ag_strength_kernel(int m, const in
     for (int p = rowptr[v] + t, p1 = rowptr[v + 1]; p < p1; p += G) {
       const int j = colind[p];
       const T a = values[p];
-      const bool s = j != v && a * a >= lhs_d * ag_abs(d[j]);
+      const bool s = ag_is_strong(a, lhs_d, d[j], j, v);
       strong[p] = s ? 1 : 0;
       n += s ? 1u : 0u;
     }
@@ -348,13 +308,6 @@ __global__ __launch_bounds__(256) void ag_prolongator_kernel(int64_t m, const in
 }
 
 // ---- coarsen
-__global__ __launch_bounds__(256) void cz_check_agg_kernel(int64_t m, const int32_t* __restrict__ agg, int64_t n_agg,
-                                                           int32_t* __restrict__ flag) {
-  const int64_t i = (int64_t) blockIdx.x * 256 + threadIdx.x;
-  if (i < m && (agg[i] < 0 || agg[i] >= n_agg))
-    flag[0] = 1;
-}
-
 // out[p] = agg[in[p]]; pos[p] = p when given
 __global__ __launch_bounds__(256) void cz_rename_kernel(int64_t nnz, const int32_t* __restrict__ agg, const int32_t* __restrict__ in,
                                                         int32_t* __restrict__ out, int32_t* __restrict__ pos) {
@@ -363,42 +316,6 @@ __global__ __launch_bounds__(256) void cz_rename_kernel(int64_t nnz, const int32
     if (pos)
       pos[p] = (int32_t) p;
   }
-}
-
-// head[] arrives zeroed: the first sorted position of every non-empty coarse row
-__global__ __launch_bounds__(256) void cz_row_start_kernel(int64_t n_agg, const int32_t* __restrict__ s_rowptr,
-                                                           int32_t* __restrict__ head) {
-  const int64_t i = (int64_t) blockIdx.x * 256 + threadIdx.x;
-  if (i < n_agg && s_rowptr[i] < s_rowptr[i + 1])
-    head[s_rowptr[i]] = 1;
-}
-
-// ... and every position whose coarse column differs from its predecessor's (head[q] is touched by thread q alone)
-__global__ __launch_bounds__(256) void cz_heads_kernel(int64_t nnz, const int32_t* __restrict__ s_col, int32_t* __restrict__ head) {
-  for (int64_t q = (int64_t) blockIdx.x * 256 + threadIdx.x; q < nnz; q += (int64_t) gridDim.x * 256)
-    if (q > 0 && s_col[q] != s_col[q - 1])
-      head[q] = 1;
-}
-
-// rank[] = the exclusive scan of the head flags (nnz + 1 entries): position q heads coarse entry rank[q] iff rank[q + 1] != rank[q]
-__global__ __launch_bounds__(256) void cz_emit_kernel(int64_t nnz, const int32_t* __restrict__ rank, const int32_t* __restrict__ s_col,
-                                                      int32_t* __restrict__ seg_ptr, int32_t* __restrict__ c_colind) {
-  for (int64_t q = (int64_t) blockIdx.x * 256 + threadIdx.x; q < nnz; q += (int64_t) gridDim.x * 256) {
-    const int e = rank[q];
-    if (rank[q + 1] != e) {
-      seg_ptr[e] = (int32_t) q;
-      c_colind[e] = s_col[q];
-    }
-    if (q == nnz - 1)
-      seg_ptr[rank[nnz]] = (int32_t) nnz;
-  }
-}
-
-__global__ __launch_bounds__(256) void cz_rowptr_kernel(int64_t n_agg, const int32_t* __restrict__ s_rowptr,
-                                                        const int32_t* __restrict__ rank, int32_t* __restrict__ c_rowptr) {
-  const int64_t i = (int64_t) blockIdx.x * 256 + threadIdx.x;
-  if (i <= n_agg)
-    c_rowptr[i] = rank[s_rowptr[i]];
 }
 
 // c[e] = the terms of coarse entry e added one after the other in ascending sorted position, from the first term

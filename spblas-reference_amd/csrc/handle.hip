@@ -27,6 +27,7 @@ void preload_ilu0();
 void preload_multicolor();
 void preload_gauss_seidel();
 void preload_aggregate();
+void preload_smooth();
 void preload_multigpu();
 } // namespace spb
 
@@ -94,6 +95,7 @@ int spblas_gfx950_create(spblas_gfx950_handle_t* handle, void* stream) {
       spb::preload_multicolor();
       spb::preload_gauss_seidel();
       spb::preload_aggregate();
+      spb::preload_smooth();
       spb::preload_multigpu();
     });
   return SPBLAS_GFX950_STATUS_SUCCESS;
